@@ -7,7 +7,8 @@ the two 64x64 factor matrices are broadcast once from rank 0 over RCCL).  One st
 fq_kron_quant_f16 (packed INT4 + fp16 scales out) over one 128 MiB activation buffer already resident in
 HBM; buffers rotate over > 256 MiB so the Infinity Cache cannot serve the stream.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C2S|C1|C3|C4|C4H|C5] [--dtype f16|bf16]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C2S|C1|C3|C4|C4H|C5] [--dtype f16|bf16] [--full]
+                  [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
 `--gpus N` with N > 1 and no launcher around it (WORLD_SIZE unset) LAUNCHES the N ranks itself (`launch_ranks`: one process per
@@ -33,9 +34,13 @@ an external launcher `--gpus` must equal WORLD_SIZE. Either way stdout is exactl
       [8 x 16384, 2048] in 256 groups (Zipf routing) through the grouped 32x64 launch with per-expert clip pairs;
       experts (groups) and tokens sharded over the GPUs (strong scaling).
 
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` (HBM, algorithmic bytes / HIP-
-event time per launch of the dominant kernel) and `cpu_baseline` (torch restatement of the reference's CPU fake-quant
-path, timed on the host cores, bounded sample).
+A plain run sets up, settles, warms up, times the K steps and prints ONE JSON line from rank 0: `metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` (wall clock of one timed step) and the set-up facts of the run. `--full` adds, after
+the timed steps, what takes passes of its own: `roofline` (HBM, algorithmic bytes / time per launch of the dominant kernel,
+per-launch quantiles, the stream floor), the `strong` / `c4` sub-records of the default config and `cpu_baseline` (torch
+restatement of the reference's CPU fake-quant path, timed on the host cores, bounded sample). `--dump-outputs DIR` writes
+what the last timed step computed (C1 / C2 / C2S) as float32 .npy files; the inputs are seeded, so two builds compare
+output for output.
 """
 import argparse
 import ctypes
@@ -193,6 +198,7 @@ class Workload:
     scaling = "weak"
     graph = False
     graph_inputs = 1   # graphs captured when `graph` (one per rotating input set)
+    outputs = None     # outputs(i) -> {name: tensor} what step i handed its caller (--dump-outputs); None: not exposed
 
 
 class C2(Workload):
@@ -268,6 +274,11 @@ class C2(Workload):
                        "activation_dtype": dtype, "fragment_image": "prepared once (FQ_WS_PREPARED)"}
         if self.fakequant:
             self.floor_us = None   # (the streaming probe moves the packed contract's byte mix)
+
+    def outputs(self, i):
+        if self.fakequant:
+            return {"fakequant": self.fqs[i % N_BUF]}
+        return {"q_int4": self.qs[i % N_BUF], "scales": self.ss[i % N_BUF]}
 
     def floor_us(self, stream):
         """practical HBM floor: the same bytes (8 KB in, 2 KB + 2 B out per token) moved by a no-arithmetic kernel"""
@@ -537,9 +548,8 @@ def reduce_over_ranks(dist, device, wall_s, kern_ms, elems, force=False):
     return float(t[0]), float(t[1]), float(e[0]), per_rank
 
 
-def timed_region(step, steps, warmup, dist, stream):
-    """W untimed warm-up steps, then EXACTLY K steps between barrier + synchronize on both sides -> (wall seconds, average step
-    in ms from HIP events on the launch stream — of an identical K-step pass right behind the wall-clocked one)."""
+def timed_region(step, steps, warmup, dist):
+    """W untimed warm-up steps, then EXACTLY K steps between barrier + synchronize on both sides -> wall seconds."""
     for i in range(warmup):
         step(i)
     torch.cuda.synchronize()
@@ -554,6 +564,11 @@ def timed_region(step, steps, warmup, dist, stream):
     if dist is not None:                # the closing barrier + synchronize of the bracket: behind the clock — an RCCL barrier is an
         dist.barrier()                  # all-reduce of its own (~0.2 ms measured in a one-rank group: a third of 20 steps of 35 us)
     torch.cuda.synchronize()
+    return wall
+
+
+def event_pass(step, steps, stream):
+    """Average step in ms from HIP events on the launch stream, over an identical K-step pass run right behind timed_region (--full)."""
     # The HIP-event figure of the same K steps, from an IDENTICAL pass right behind the wall-clocked one (round 6, third session): an event record
     # is a packet of its own on this runtime — the two records inside the wall-clocked bracket cost it ~0.5 us per step at K = 20
     # (tools/microbench/bracket_probe.py: 34.6 us with them, 34.1 without, events 33.7, K = 1000 33.7) — so the wall clock no longer carries them.
@@ -563,7 +578,34 @@ def timed_region(step, steps, warmup, dist, stream):
         step(i)
     ev1.record(stream)
     torch.cuda.synchronize()
-    return wall, ev0.elapsed_time(ev1) / steps
+    return ev0.elapsed_time(ev1) / steps
+
+
+DUMP_ROWS = 2048     # --dump-outputs: a fixed, seeded sample of this many rows of a [rows, d] output (2048 x 4096 float32 = 32 MiB)
+
+
+def snapshot_outputs(wl, i):
+    """Device copies of what step i handed its caller (a seeded sample of DUMP_ROWS rows of each [rows, ...] output), taken right
+    after the timed region so that no later pass can touch them; write_outputs() turns them into float32 .npy files."""
+    snap = {}
+    for name, t in wl.outputs(i).items():
+        if t.dim() == 2 and t.shape[0] > DUMP_ROWS:
+            rows = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(0))[:DUMP_ROWS].sort().values
+            t = t.index_select(0, rows.to(t.device))
+        snap[name] = t.clone()
+    torch.cuda.synchronize()
+    return snap
+
+
+def write_outputs(snap, out_dir):
+    """packed INT4 bytes -> their signed digits (oracle.fq_oracle.unpack_i4, even column = low nibble); everything else as is."""
+    import numpy as np
+    from oracle import fq_oracle
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in snap.items():
+        a = t.cpu()
+        a = fq_oracle.unpack_i4(a.numpy()) if a.dtype == torch.uint8 else a.float().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32))
 
 
 def capture_graphs(wl, device):
@@ -590,7 +632,8 @@ def sub_record(cls, steps, warmup, device, rank, world, sharding, dist, force=Fa
     wl = cls(device, rank, world, sharding, bc)
     step = capture_graphs(wl, device) if wl.graph else wl.step
     stream = torch.cuda.current_stream(device)
-    wall, kern_ms = timed_region(step, steps, warmup, dist, stream)
+    wall = timed_region(step, steps, warmup, dist)
+    kern_ms = event_pass(step, steps, stream)
     wall, kern_ms, elems, per_rank = reduce_over_ranks(dist, device, wall, kern_ms, wl.elems, force)
     rec = None
     if rank == 0:
@@ -697,9 +740,15 @@ def main(argv=None):
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--config", default="C2", choices=sorted(WORKLOADS))
     ap.add_argument("--dtype", default="f16", choices=["f16", "bf16"], help="activation dtype (C1 / C2 / C5)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything beyond the headline figure: the HIP-event pass, per-launch quantiles, "
+                         "per-kernel times, the HBM stream floor, `roofline`, the sub-records and `cpu_baseline`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy, float32 (C1 / C2 / C2S; rank 0): C2 q_int4 "
+                         f"(signed INT4 digits) + scales, C1 fakequant; [rows, d] outputs as a fixed seeded sample of {DUMP_ROWS} rows")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip `cpu_baseline`")
     ap.add_argument("--no-sub-records", action="store_true",
-                    help="default config only: skip the `strong` (C2S x 32 layers, one multi-job launch) and `c4` sub-records")
+                    help="--full, default config only: skip the `strong` (C2S x 32 layers, one multi-job launch) and `c4` sub-records")
     ap.add_argument("--force-dist", action="store_true",
                     help="single process: run inside a ONE-rank RCCL group anyway (init, the set-up broadcast, barriers, the reductions): "
                          "the N > 1 code path on a single-GPU box; the line then carries a `dist` record")
@@ -717,6 +766,10 @@ def main(argv=None):
         args.warmup = {"C1": 100, "C2": 200, "C2S": 200, "C3": 10, "C4": 2, "C4H": 2, "C5": 5, "C2SL": 10}[args.config]
     if args.dtype != "f16" and args.config not in ("C1", "C2", "C5"):
         ap.error("--dtype bf16 goes with --config C1 / C2 / C5 (C3 / C4 are the deploy configs: fp16 contracts of the reference)")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs is not None and WORKLOADS[args.config].outputs is None:
+        ap.error(f"--dump-outputs: --config {args.config} does not expose its outputs (C1 / C2 / C2S do)")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -769,48 +822,53 @@ def main(argv=None):
                 step(i)
             settle_launches += chunk
             torch.cuda.synchronize()
-    wall, kern_ms = timed_region(step, args.steps, args.warmup, dist, stream)
+    wall = timed_region(step, args.steps, args.warmup, dist)
+    snap = snapshot_outputs(wl, args.steps - 1) if (args.dump_outputs is not None and rank == 0) else None
 
-    # Per-step distribution (the reference's own quantiles, deploy/kernels/kron_matmul.py:269-281): a SEPARATE
-    # untimed pass of the same K steps with one event pair per step, so that the timed region above carries no
-    # event markers between its launches. median / p20 / p80 in microseconds.
-    evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
-    evs[0].record(stream)
-    for i in range(args.steps):
-        step(i)
-        evs[i + 1].record(stream)
-    torch.cuda.synchronize()
-    per = sorted(evs[i].elapsed_time(evs[i + 1]) * 1e3 for i in range(args.steps))
-    quant = lambda f: per[min(len(per) - 1, int(f * len(per)))]
-    per_launch = {"median_us": quant(0.5), "p20_us": quant(0.2), "p80_us": quant(0.8), "min_us": per[0], "max_us": per[-1]}
+    kern_ms = 0.0
+    if args.full:
+        kern_ms = event_pass(step, args.steps, stream)
 
-    # the individual launches of a step, each timed back to back on its own (HIP events): names the dominant kernel
-    kern_us = []
-    for name, fn, nbytes in wl.kernels:
-        reps = max(10, min(200, args.steps))
-        for i in range(3):
-            fn(i)
+        # Per-step distribution (the reference's own quantiles, deploy/kernels/kron_matmul.py:269-281): a SEPARATE
+        # untimed pass of the same K steps with one event pair per step, so that the timed region above carries no
+        # event markers between its launches. median / p20 / p80 in microseconds.
+        evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+        evs[0].record(stream)
+        for i in range(args.steps):
+            step(i)
+            evs[i + 1].record(stream)
         torch.cuda.synchronize()
-        # (round 6) three windows of `reps` launches, the MEDIAN window: one stall (an allocator growth, a clock step) inside a 10-launch window
-        # once read 3479 us for a 123 us kernel (profiles/r06_bench_C4H.json)
-        wins = []
-        for _ in range(3):
-            k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            k0.record(torch.cuda.current_stream(device))
-            for i in range(reps):
+        per = sorted(evs[i].elapsed_time(evs[i + 1]) * 1e3 for i in range(args.steps))
+        quant = lambda f: per[min(len(per) - 1, int(f * len(per)))]
+        per_launch = {"median_us": quant(0.5), "p20_us": quant(0.2), "p80_us": quant(0.8), "min_us": per[0], "max_us": per[-1]}
+
+        # the individual launches of a step, each timed back to back on its own (HIP events): names the dominant kernel
+        kern_us = []
+        for name, fn, nbytes in wl.kernels:
+            reps = max(10, min(200, args.steps))
+            for i in range(3):
                 fn(i)
-            k1.record(torch.cuda.current_stream(device))
             torch.cuda.synchronize()
-            wins.append(k0.elapsed_time(k1) / reps * 1e3)
-        kern_us.append((name, sorted(wins)[1], nbytes))
-    floor_us = wl.floor_us(stream) if (rank == 0 and getattr(wl, "floor_us", None) is not None) else None
+            # (round 6) three windows of `reps` launches, the MEDIAN window: one stall (an allocator growth, a clock step) inside a 10-launch window
+            # once read 3479 us for a 123 us kernel (profiles/r06_bench_C4H.json)
+            wins = []
+            for _ in range(3):
+                k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                k0.record(torch.cuda.current_stream(device))
+                for i in range(reps):
+                    fn(i)
+                k1.record(torch.cuda.current_stream(device))
+                torch.cuda.synchronize()
+                wins.append(k0.elapsed_time(k1) / reps * 1e3)
+            kern_us.append((name, sorted(wins)[1], nbytes))
+        floor_us = wl.floor_us(stream) if (rank == 0 and getattr(wl, "floor_us", None) is not None) else None
 
     wall, kern_ms, elems_total, per_rank_wall = reduce_over_ranks(dist, device, wall, kern_ms, wl.elems, args.force_dist)
 
     # (round 4) the STRONG-scaling sub-records of the default line: the driver only ever runs `bench.py --gpus N`, whose headline
     # value is weak scaling (every GPU its own 8 x 2048 tokens)
     subs = {}
-    if args.config == "C2" and args.dtype == "f16" and not args.no_sub_records:
+    if args.full and args.config == "C2" and args.dtype == "f16" and not args.no_sub_records:
         del wl.xs
         torch.cuda.empty_cache()
         if world > 1 or args.force_dist:
@@ -824,15 +882,6 @@ def main(argv=None):
     if rank == 0:
         ms_per_step = wall * 1e3 / args.steps
         value = elems_total / (wall / args.steps) / 1e6
-        ev_us = None
-        if args.config in ("C1", "C2", "C2S"):               # one launch per step: the timed region IS the kernel
-            # (round 6) ONE clock: the roofline figure of the line follows from the same wall clock as `value` and
-            # `ms_per_step` (launch gaps included: the kinder event clock of the same region stays beside it as *_events)
-            dom_name, dom_us, dom_bytes = wl.kernels[0][0], ms_per_step * 1e3, wl.kernels[0][2]
-            ev_us = kern_ms * 1e3
-        else:
-            dom_name, dom_us, dom_bytes = max(kern_us, key=lambda k: k[1])
-        achieved = dom_bytes / (dom_us * 1e-6) / 1e9
         out = {
             "metric": wl.metric, "value": value, "unit": "Melem/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": wl.scaling,
@@ -841,30 +890,42 @@ def main(argv=None):
             "per_rank_ms_per_step": [w * 1e3 / args.steps for w in per_rank_wall],
             "broadcast_ms": bcast.ms, "broadcast_bytes": bcast.bytes,
             "dist": None if dist is None else {"backend": dist.get_backend(), "world_size": dist.get_world_size(), "forced_single_rank": bool(args.force_dist and world == 1)},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": pmc_traffic()[0] if (args.config == "C2" and args.dtype == "f16") else None,
-                         "traffic_source": pmc_traffic()[1] if (args.config == "C2" and args.dtype == "f16") else None,
-                         "kernel": dom_name, "algorithmic_bytes_per_launch": dom_bytes,
-                         "launch_us": dom_us, "clock": "wall (ms_per_step)" if ev_us is not None else "hip events, the kernel alone back to back",
-                         "launch_us_events": ev_us, "achieved_events": (dom_bytes / (ev_us * 1e-6) / 1e9) if ev_us else None,
-                         "frac_events": (dom_bytes / (ev_us * 1e-6) / 1e9 / HBM_PEAK_GBS) if ev_us else None,
-                         "events_pass": "HIP events around an identical K-step pass right behind the wall-clocked one (an event record is a packet of its own: inside the wall-clocked bracket the two records cost ~0.5 us per step at K = 20)",
-                         "per_launch": per_launch, "hbm_stream_floor_us": floor_us,
-                         "frac_of_stream_floor": (floor_us / dom_us) if floor_us else None},
         }
-        if args.config not in ("C1", "C2"):
-            step_bytes = sum(k[2] for k in wl.kernels) * (wl.config.get("layers", 1))
-            out["roofline"]["step"] = {"algorithmic_bytes": step_bytes, "step_us": kern_ms * 1e3,
-                                       "frac": step_bytes / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS}
-            out["roofline"]["kernels"] = [{"kernel": n, "launch_us": u, "algorithmic_bytes": b,
-                                           "frac": b / (u * 1e-6) / 1e9 / HBM_PEAK_GBS} for n, u, b in kern_us]
-        for k, v in subs.items():
-            out[k] = v
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(*{"C1": (20.0, 64, 64), "C2": (20.0, 64, 64), "C2S": (20.0, 64, 64), "C3": (20.0, 64, 64),
-                                                 "C4": (20.0, 64, 128), "C4H": (20.0, 64, 128), "C5": (20.0, 32, 64),
-                                                 "C2SL": (20.0, 64, 64)}[args.config])
+        if args.full:
+            ev_us = None
+            if args.config in ("C1", "C2", "C2S"):               # one launch per step: the timed region IS the kernel
+                # (round 6) ONE clock: the roofline figure of the line follows from the same wall clock as `value` and
+                # `ms_per_step` (launch gaps included: the kinder event clock of the same region stays beside it as *_events)
+                dom_name, dom_us, dom_bytes = wl.kernels[0][0], ms_per_step * 1e3, wl.kernels[0][2]
+                ev_us = kern_ms * 1e3
+            else:
+                dom_name, dom_us, dom_bytes = max(kern_us, key=lambda k: k[1])
+            achieved = dom_bytes / (dom_us * 1e-6) / 1e9
+            out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBS,
+                               "traffic": pmc_traffic()[0] if (args.config == "C2" and args.dtype == "f16") else None,
+                               "traffic_source": pmc_traffic()[1] if (args.config == "C2" and args.dtype == "f16") else None,
+                               "kernel": dom_name, "algorithmic_bytes_per_launch": dom_bytes,
+                               "launch_us": dom_us, "clock": "wall (ms_per_step)" if ev_us is not None else "hip events, the kernel alone back to back",
+                               "launch_us_events": ev_us, "achieved_events": (dom_bytes / (ev_us * 1e-6) / 1e9) if ev_us else None,
+                               "frac_events": (dom_bytes / (ev_us * 1e-6) / 1e9 / HBM_PEAK_GBS) if ev_us else None,
+                               "events_pass": "HIP events around an identical K-step pass right behind the wall-clocked one (an event record is a packet of its own: inside the wall-clocked bracket the two records cost ~0.5 us per step at K = 20)",
+                               "per_launch": per_launch, "hbm_stream_floor_us": floor_us,
+                               "frac_of_stream_floor": (floor_us / dom_us) if floor_us else None}
+            if args.config not in ("C1", "C2"):
+                step_bytes = sum(k[2] for k in wl.kernels) * (wl.config.get("layers", 1))
+                out["roofline"]["step"] = {"algorithmic_bytes": step_bytes, "step_us": kern_ms * 1e3,
+                                           "frac": step_bytes / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS}
+                out["roofline"]["kernels"] = [{"kernel": n, "launch_us": u, "algorithmic_bytes": b,
+                                               "frac": b / (u * 1e-6) / 1e9 / HBM_PEAK_GBS} for n, u, b in kern_us]
+            for k, v in subs.items():
+                out[k] = v
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline(*{"C1": (20.0, 64, 64), "C2": (20.0, 64, 64), "C2S": (20.0, 64, 64), "C3": (20.0, 64, 64),
+                                                     "C4": (20.0, 64, 128), "C4H": (20.0, 64, 128), "C5": (20.0, 32, 64),
+                                                     "C2SL": (20.0, 64, 64)}[args.config])
+        if snap is not None:
+            write_outputs(snap, args.dump_outputs)
         if json_fd is None:
             print(json.dumps(out))
         else:

@@ -25,14 +25,14 @@ alg = TOKENS * (2 * D + D // 2 + 2)
 out = {
     "kernel": "fq_kron64_kernel<FQ_OUT_PACKED, f16> (prepared 16 KB fragment image)",
     "workload": "C2: 16384 tokens x d=4096, packed out",
-    "source": f"tools/prof.sh {tag} (rocprofv3 --kernel-trace --stats of `bench.py --no-cpu-baseline --no-sub-records`; --pmc in separate passes of "
-              f"`bench.py --steps 200 --warmup 100 --no-cpu-baseline --no-sub-records`), see {tag}_kron64_prof_summary.txt; assembled by tools/pmc_json.py",
+    "source": f"tools/prof.sh {tag} (rocprofv3 --kernel-trace --stats of `bench.py --full --no-cpu-baseline --no-sub-records`; --pmc in separate passes of "
+              f"`bench.py --steps 200 --warmup 100 --full --no-cpu-baseline --no-sub-records`), see {tag}_kron64_prof_summary.txt; assembled by tools/pmc_json.py",
     "FETCH_SIZE_KB_avg": vals.get("FETCH_SIZE"),
     "WRITE_SIZE_KB_avg": vals.get("WRITE_SIZE"),
     "hbm_bytes_per_launch": int(round((2 * vals["FETCH_SIZE"] + vals["WRITE_SIZE"]) * 1024)) if "FETCH_SIZE" in vals and "WRITE_SIZE" in vals else None,
     "note": "gfx950: FETCH_SIZE reports half of a wide coalesced read stream (MI355X_MICROARCH.md HBM) -> doubled; WRITE_SIZE as reported",
     "algorithmic_bytes_per_launch": alg,
-    "kernel_trace": dict(trace or {}, command="rocprofv3 --kernel-trace --stats -- python bench.py --no-cpu-baseline --no-sub-records (default: 150 ms settle phase "
+    "kernel_trace": dict(trace or {}, command="rocprofv3 --kernel-trace --stats -- python bench.py --full --no-cpu-baseline --no-sub-records (default: 150 ms settle phase "
                                                 "+ 200 warm-up + 1000 timed launches + the per-launch pass)"),
     "per_token": {k: round(vals[k] / TOKENS, 1) for k in ("SQ_INSTS_VALU", "SQ_INSTS_MFMA", "SQ_INSTS_LDS", "SQ_INSTS_VMEM_RD") if k in vals},
     "sq": dict({k: vals[k] for k in ("SQ_WAVE_CYCLES", "SQ_WAIT_ANY", "SQ_WAIT_INST_ANY", "SQ_ACTIVE_INST_ANY", "SQ_ACTIVE_INST_VALU",
