@@ -71,6 +71,11 @@ int fq_kv_decode_splits(int batch, int num_heads, int seq_hint);
 int fq_kv_decode_wg_heads(int batch, int num_q_heads, int q_group, int head_dim);
 int64_t fq_kv_decode_ws_bytes_gqa(int batch, int num_q_heads, int q_group, int head_dim);
 int64_t fq_kv_decode_ws_bytes(int batch, int num_heads, int head_dim);
+int64_t fq_kv_extend_ws_bytes(int batch, int num_q_heads, int q_len, int head_dim);   // fq_kvextend.hip
+int fq_launch_kv_extend(f16* o, const f16* q, const f16* qt, int transpose_out, void* kv_data, const void* kv_param, const int* indptr,
+                        const int* indices, const int* last, int num_layers, int layer_idx, int num_cache_heads, int q_group, int copies,
+                        int q_len, int page_size, int head_dim, int batch, int seq_hint, float* ws, int64_t ws_bytes, hipStream_t stream,
+                        bool f16_cache);
 int fq_launch_silu_mul(const f16* gate, const f16* up, f16* y, int64_t n, int n_cu, hipStream_t stream);
 int fq_launch_silu_hadamard_quant(const f16* gate, const f16* up, int64_t rows, int n, int K, const f16* hadK, float scale,
                                   float sig_max, float sig_min, uint8_t* q, f16* scale_out, int n_cu, hipStream_t stream);
@@ -1311,6 +1316,37 @@ int fq_kv_batch_decode_copies(int fp16_cache, void* o, const void* q, const void
                              (const int*)last_page_offset, num_layers, layer_idx, num_heads, page_size, head_dim, batch_size,
                              (const f16*)q_trans, transpose_out != 0, (hipStream_t)stream, fp16_cache != 0, (float*)workspace, splits, copies,
                              nullptr, nullptr, nullptr, 1, copies);
+    return check_launch(rc, what);
+}
+
+int64_t fq_kv_extend_workspace_bytes(int batch_size, int num_q_heads, int q_len, int head_dim) {
+    if (batch_size < 0 || num_q_heads <= 0 || q_len < 1 || (head_dim != 64 && head_dim != 128)) return -1;
+    return fq_kv_extend_ws_bytes(batch_size, num_q_heads, q_len, head_dim);
+}
+
+int fq_kv_batch_extend(int fp16_cache, void* o, const void* q, const void* q_trans, int transpose_out, const void* kv_data,
+                       const void* kv_param, const void* kv_indptr, const void* kv_indices, const void* last_page_offset, int num_layers,
+                       int layer_idx, int num_cache_heads, int q_group, int copies, int q_len, int page_size, int head_dim, int batch_size,
+                       int seq_hint, void* workspace, int64_t workspace_bytes, void* stream) {
+    const char* what = "fq_kv_batch_extend";
+    if (q_len < 1) return fail(FQ_EINVAL, "%s: q_len=%d must be >= 1", what, q_len);
+    int rc = kv_geometry_ok(what, num_layers, layer_idx, num_cache_heads, page_size, head_dim, batch_size);
+    if (rc != FQ_OK) return rc;
+    if (q_group < 1 || q_group > 64 || copies < 1 || copies > 8 || q_group % copies || num_cache_heads % copies)
+        return fail(FQ_EINVAL, "%s: q_group=%d (1..64) must be a multiple of copies=%d (1..8), which must divide num_cache_heads=%d", what, q_group,
+                    copies, num_cache_heads);
+    if (head_dim != 128) return fail(FQ_EUNSUPPORTED, "%s: head_dim=%d (128 only)", what, head_dim);
+    if (!o || !q || !kv_data || (!fp16_cache && !kv_param) || !kv_indptr || !kv_indices || !last_page_offset)
+        return fail(FQ_EINVAL, "%s: NULL pointer", what);
+    FQ_NEED_ALIGN16(what, kv_data, q_trans, workspace);
+    const int q_heads = num_cache_heads / copies * q_group;
+    const int64_t need = fq_kv_extend_ws_bytes(batch_size, q_heads, q_len, head_dim);
+    if (workspace && need > 0 && workspace_bytes < need)
+        return fail(FQ_EINVAL, "%s: workspace of %lld bytes, fq_kv_extend_workspace_bytes says %lld", what, (long long)workspace_bytes, (long long)need);
+    rc = fq_launch_kv_extend((f16*)o, (const f16*)q, (const f16*)q_trans, transpose_out != 0, (void*)kv_data, kv_param, (const int*)kv_indptr,
+                             (const int*)kv_indices, (const int*)last_page_offset, num_layers, layer_idx, num_cache_heads, q_group, copies,
+                             q_len, page_size, head_dim, batch_size, seq_hint, (float*)workspace, workspace_bytes, (hipStream_t)stream,
+                             fp16_cache != 0);
     return check_launch(rc, what);
 }
 

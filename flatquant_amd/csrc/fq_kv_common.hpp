@@ -164,4 +164,32 @@ __device__ __forceinline__ void kv_stage_tfrag(const T* __restrict__ Tm, uint4* 
     }
 }
 
+// The decode attention's row pieces (fq_kvcache.hip), also read by the multi-token attention (fq_kvextend.hip).
+typedef const int __attribute__((address_space(4))) kv_const_int;
+constexpr int KV_PERM[8] = {0, 4, 1, 5, 2, 6, 3, 7};   // feature (within the dword's eight) of packed slot e
+__device__ __forceinline__ uint32_t kv_and_or(uint32_t x, uint32_t mask, uint32_t bits) {
+    uint32_t r;   // (gfx9: one constant-bus operand per VOP3 — the mask in an SGPR, the exponent bits in a VGPR)
+    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "s"(mask), "v"(bits));
+    return r;
+}
+// the eight nibbles of a dword as the eight EXACT fp16 values 16 + n (feature order KV_PERM)
+__device__ __forceinline__ void kv_unpack8(uint32_t w, uint32_t ebits, uint32_t (&r)[4]) {
+    constexpr uint32_t M = 0x03C003C0u;
+    r[0] = kv_and_or(w << 6, M, ebits);
+    r[1] = kv_and_or(w << 2, M, ebits);
+    r[2] = kv_and_or(w >> 2, M, ebits);
+    r[3] = kv_and_or(w >> 6, M, ebits);
+}
+// q . k of a wave's 16 cached rows (the B columns) for head_dim 128 with the first four D rows kept: lane (part, i) — which holds D rows
+// 4 part .. 4 part + 3 of column i — gets the sums of A rows 4 part .. 4 part + 3 for ITS row i in c[0..3], no lane exchange.
+__device__ __forceinline__ f32x4 kv_qk_mfma4(const f16x8 (&qa)[4], const f16x8 (&kb)[4]) {
+    f32x4 c = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int w = 0; w < 4; ++w) c = __builtin_amdgcn_mfma_f32_16x16x32_f16(qa[w], kb[w], c, 0, 0, 0);
+    return c;
+}
+__device__ __forceinline__ size_t kv_uniform64(size_t v) {
+    return ((size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)v);
+}
+
 }  // namespace fqkv

@@ -114,22 +114,14 @@ __global__ __launch_bounds__(256) void fq_kv_append_kernel(PagedKv p, const uint
     }
 }
 
-typedef const int __attribute__((address_space(4))) kv_const_int;
-constexpr int KV_PERM[8] = {0, 4, 1, 5, 2, 6, 3, 7};   // feature (within the dword's eight) of packed slot e
+// (the row loads and the nibble unpacking are shared with fq_kvextend.hip: fq_kv_common.hpp)
+using fqkv::kv_const_int;
+using fqkv::KV_PERM;
+using fqkv::kv_unpack8;
+using fqkv::kv_qk_mfma4;
+using fqkv::kv_uniform64;
 constexpr float KV_OFF = 16.0f;
 constexpr float KV_MARGIN = 8.0f;   // see the step of fq_kv_decode_kernel
-__device__ __forceinline__ uint32_t kv_and_or(uint32_t x, uint32_t mask, uint32_t bits) {
-    uint32_t r;   // (gfx9: one constant-bus operand per VOP3 — the mask in an SGPR, the exponent bits in a VGPR)
-    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "s"(mask), "v"(bits));
-    return r;
-}
-__device__ __forceinline__ void kv_unpack8(uint32_t w, uint32_t ebits, uint32_t (&r)[4]) {
-    constexpr uint32_t M = 0x03C003C0u;
-    r[0] = kv_and_or(w << 6, M, ebits);
-    r[1] = kv_and_or(w << 2, M, ebits);
-    r[2] = kv_and_or(w >> 2, M, ebits);
-    r[3] = kv_and_or(w >> 6, M, ebits);
-}
 // acc += float(half h of the packed pair) * s: v_fma_mix_f32 reads the fp16 half directly (a convert + an FMA otherwise)
 template <int HI>
 __device__ __forceinline__ void kv_fma_half(float& acc, uint32_t pair, float s) {
@@ -153,14 +145,6 @@ __device__ __forceinline__ float kv_qk_mfma(const f16x8 (&qa)[4], const f16x8 (&
         return c[0];
     }
 }
-// The same for head_dim 128 with the first four D rows kept: with A row m = the query of head m % QG (fq_kv_decode_kernel<.., QG>), lane
-// (part, i) — which holds D rows 4 part .. 4 part + 3 of column i — gets the sums of heads 0 .. 3 for ITS row i in c[0..3], no lane exchange.
-__device__ __forceinline__ f32x4 kv_qk_mfma4(const f16x8 (&qa)[4], const f16x8 (&kb)[4]) {
-    f32x4 c = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int w = 0; w < 4; ++w) c = __builtin_amdgcn_mfma_f32_16x16x32_f16(qa[w], kb[w], c, 0, 0, 0);
-    return c;
-}
 template <int QL>
 __device__ __forceinline__ float kv_qk(const f16x8 (&qa)[4], const uint4 kq, uint32_t ebits) {   // INT4 row -> sum_j q_j (16 + n_ij)
     const uint32_t kw[4] = {kq.x, kq.y, kq.z, kq.w};
@@ -172,10 +156,6 @@ __device__ __forceinline__ float kv_qk(const f16x8 (&qa)[4], const uint4 kq, uin
         kb[w] = __builtin_bit_cast(f16x8, u32x4{r[0], r[1], r[2], r[3]});
     }
     return kv_qk_mfma<QL>(qa, kb);
-}
-
-__device__ __forceinline__ size_t kv_uniform64(size_t v) {
-    return ((size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)v);
 }
 
 // the split decode's workspace: a counter per (request, head) pair first (a fixed place, whatever the split count), the states behind them

@@ -97,8 +97,9 @@ FUSE_APPEND_MAX_PAIRS = 1024
 class MultiLayerPagedKVCache4Bit:
     """kv_cache.py:166-392 with the same constructor arguments, page / scale tensors and ``update`` contract: the first call
     per layer stores the (transformed, quantised) prompt keys / values and returns the fp16 key / value states for the prefill
-    attention; every later call appends one token per request and returns a callable that runs the decode attention for the
-    layer's query ([bsz, 1, heads, head_dim] -> the same shape).
+    attention; every later call appends its tokens per request and returns a callable that runs the attention for the layer's
+    query: one token ([bsz, 1, heads, head_dim] -> the same shape) the decode attention, T > 1 tokens (extension: a speculative verify, a
+    follow-up prompt, a prompt fed in pieces; [bsz, T, heads, head_dim]) causal attention over the cache (ops.kv_batch_extend).
 
     * ``disable_quant=False``: the INT4 cache (uint8 pages of head_dim / 2 bytes per row + (scale, zero) per row);
       ``disable_quant=True``: the fp16 configuration (:177-190, init_kv_f16 / append_kv_f16 / batch_decode_f16): fp16 pages,
@@ -292,6 +293,52 @@ class MultiLayerPagedKVCache4Bit:
             k, v, tk16, args, layer_idx, group = pend
             ops.kv_quant_append(k, v, tk16, *args, layer_idx, group)
 
+    def _step_indptr(self, b, added, device):
+        """[0, added, 2 added, ..] int32: the seqlen_indptr of a step that appends ``added`` tokens per request. One tensor per step size, kept
+        for the cache's life: a captured step (deploy.graphed) holds its address, and steps of several sizes may alternate (a verify step,
+        decode steps, a chunked prompt's last piece). Made inside a capture, it stays that graph's own (its memory is the graph's, its values are
+        written when the graph replays)."""
+        key = (b, added, str(device))
+        memo = self.__dict__.setdefault("_step_indptr_memo", {})
+        t = memo.get(key)
+        if t is None:
+            t = torch.arange(b + 1, device=device, dtype=torch.int32) * added
+            if not torch.cuda.is_current_stream_capturing():
+                memo[key] = t
+        return t
+
+    def _unit_params(self, rows, heads, device):
+        """(scale, zero) = (1, 0) for ``rows`` x ``heads`` fp16 rows (:270-274): prefixes of ONE buffer, so that steps of every size read the same
+        address — a captured step holds it. Replaced only when a step needs more rows than any before; then ``generation`` moves and graphs
+        captured over the old buffer go stale (deploy.graphed re-captures them), as when the pages grow."""
+        buf = self.__dict__.get("_unit_buf")
+        if buf is None or buf.shape[0] < rows or buf.shape[1] != heads or buf.device != torch.device(device):
+            n = max(rows, 2 * buf.shape[0]) if (buf is not None and buf.shape[1] == heads) else rows
+            one = torch.tensor([1.0, 0.0], dtype=torch.float16, device=device)
+            self._unit_buf = one.expand(n, heads, 2).contiguous()
+            if buf is not None:
+                self.generation += 1
+        return self._unit_buf[:rows]
+
+    def _extend_closure(self, added, args, layer_idx, had, tk_inv_t, copies):
+        """The attention of a step that appended ``added`` > 1 tokens per request (a speculative verify, a follow-up prompt, a prompt fed
+        in pieces): the closure takes q [bsz, added, heads, head_dim] and runs causal attention over the cache — token t of the step sees
+        the rows before the step and the step's tokens 0 .. t (ops.kv_batch_extend, fq_kv_batch_extend)."""
+        length_now = self.length
+
+        def attend(q, transposed=False):
+            """q [bsz, added, heads, head_dim] -> the attention output of the same shape, or [bsz, added, head_dim, heads] with ``transposed``."""
+            if q.dim() != 4 or q.shape[1] != added:
+                raise ValueError(f"the step appended {added} tokens per request: q must be [bsz, {added}, heads, head_dim], got {tuple(q.shape)}")
+            q2 = q.to(torch.float16)
+            qt = None
+            if had:
+                q2 = ops.hadamard(q2.contiguous())
+            elif tk_inv_t is not None:
+                qt = self._as_f16(tk_inv_t)
+            return ops.kv_batch_extend(q2.contiguous(), *args, layer_idx, qt, transposed, seq_hint=length_now, kv_copies=copies)
+        return attend
+
     def update(self, key_states, value_states, layer_idx, cache_kwargs=None):
         self._flush_pending()
         cache_kwargs = cache_kwargs or {}
@@ -336,11 +383,7 @@ class MultiLayerPagedKVCache4Bit:
             keys_t = key_states.to(torch.float16) if tk16 is None else torch.matmul(key_states.to(torch.float16), tk16)
             if self.disable_quant:                                      # :270-274: fp16 rows, (scale, zero) = (1, 0)
                 kq, vq = keys_t.contiguous(), value_states.to(torch.float16).contiguous()
-                pk = (b, added, heads, kq.device)
-                if getattr(self, "_unit_param_key", None) != pk:   # (kept: a host-to-device copy per step otherwise, and no graph capture)
-                    one = torch.tensor([1.0, 0.0], dtype=torch.float16, device=kq.device)
-                    self._unit_param, self._unit_param_key = one.expand(b, added, heads, 2).contiguous(), pk
-                kp = vp = self._unit_param
+                kp = vp = self._unit_params(b * added, heads, kq.device)   # (kept: a host-to-device copy per step otherwise, and no graph capture)
             else:
                 kq, kp = ops.kv_quant(keys_t.contiguous())
                 vq, vp = ops.kv_quant(value_states.to(torch.float16).contiguous())
@@ -356,9 +399,9 @@ class MultiLayerPagedKVCache4Bit:
                     indptr = torch.arange(b + 1, device=kq.device, dtype=torch.int32) * added
                 ops.kv_append(*args, kq.contiguous(), vq.contiguous(), kp.contiguous(), vp.contiguous(), layer_idx,
                               indptr.contiguous(), self.group_size)
-            else:
-                ops.kv_append(*args, kq.contiguous(), vq.contiguous(), kp.contiguous(), vp.contiguous(), layer_idx, None,
-                              self.group_size)
+            else:   # (several tokens per request: each request's `added` rows end at its length, as the prompt's do)
+                ops.kv_append(*args, kq.contiguous(), vq.contiguous(), kp.contiguous(), vp.contiguous(), layer_idx,
+                              None if added == 1 else self._step_indptr(b, added, kq.device), self.group_size)
         if init:
             self._needs_init[layer_idx] = False
             if self.disable_quant:
@@ -366,7 +409,8 @@ class MultiLayerPagedKVCache4Bit:
             if keys_t is None:
                 keys_t = key_states if tk16 is None else torch.matmul(key_states.to(torch.float16), tk16)
             return keys_t, value_states                                 # :280-281,341-344: the un-quantised states for prefill
-        assert added == 1
+        if added > 1:
+            return self._extend_closure(added, args, layer_idx, had, tk_inv_t, copies)
         length_now = self.length                                          # (an upper bound of every request's rows: the split decode's hint)
 
         def attend(q, transposed=False):

@@ -1843,6 +1843,45 @@ def kv_batch_decode(q: torch.Tensor, kv_data: torch.Tensor, kv_param: torch.Tens
     return o
 
 
+def kv_batch_extend(q: torch.Tensor, kv_data: torch.Tensor, kv_param: torch.Tensor, kv_indptr: torch.Tensor,
+                    kv_indices: torch.Tensor, last_page_offset: torch.Tensor, layer_idx: int,
+                    q_trans: Optional[torch.Tensor] = None, transpose_out: bool = False, seq_hint: int = 0, split: bool = True,
+                    kv_copies: int = 1) -> torch.Tensor:
+    """Causal attention of the T tokens a step appended to every request (fq_kv_batch_extend, round 7): q [batch, T, heads, head_dim]
+    fp16 -> o of the same shape ([batch, T, head_dim, heads] with ``transpose_out``). The lengths already count the T new rows; token t
+    attends rows 0 .. length - T + t. Heads, ``q_trans``, ``seq_hint``, ``split`` and ``kv_copies`` as kv_batch_decode: heads = cache heads
+    x q_group (a cache that holds the KV heads once) or, with ``kv_copies`` = g > 1, the replicated layout read one copy per group.
+    head_dim 128."""
+    _chk(q, "q"), _chk(kv_data, "kv_data", kv_data.dtype), _chk(kv_param, "kv_param")
+    n_layers, kv_heads, page_size, hd = _kv_geometry(kv_data)
+    batch = _chk_kv_index(kv_indptr, kv_indices, last_page_offset)
+    f16_cache = kv_data.dtype == torch.float16
+    if q.dim() != 4 or q.shape[0] != batch or q.shape[3] != hd or q.shape[1] < 1 or q.shape[2] % kv_heads:
+        raise ValueError(f"q must be [{batch}, q_len >= 1, a multiple of {kv_heads}, {hd}]")
+    q_len, heads = q.shape[1], q.shape[2]
+    q_group = heads // kv_heads
+    if kv_copies > 1:
+        if q_group != 1 or kv_heads % kv_copies or kv_copies > 8:
+            raise ValueError(f"kv_copies={kv_copies}: needs a replicated cache (query heads == cache heads == {kv_heads}) in groups of at most 8")
+        q_group = kv_copies
+    if q_trans is not None:
+        _chk(q_trans, "q_trans")
+        if q_trans.shape != (hd, hd):
+            raise ValueError("q_trans must be [head_dim, head_dim]")
+    o = torch.empty((batch, q_len, hd, heads) if transpose_out else (batch, q_len, heads, hd), dtype=torch.float16, device=q.device)
+    if batch == 0:
+        return o
+    with _on(q.device):
+        nbytes = int(lib.fq_kv_extend_workspace_bytes(batch, heads, q_len, hd)) if split else 0
+        stream = _stream(q)
+        ws = _kv_split_workspace(("extend", q.device.index, stream.value, batch, heads, q_len, hd), nbytes, q.device) if nbytes > 0 else None
+        check(lib.fq_kv_batch_extend(1 if f16_cache else 0, _ptr(o), _ptr(q), _ptr(q_trans), 1 if transpose_out else 0, _ptr(kv_data),
+                                     _ptr(kv_param), _ptr(kv_indptr), _ptr(kv_indices), _ptr(last_page_offset), n_layers, layer_idx,
+                                     kv_heads, q_group, kv_copies, q_len, page_size, hd, batch, int(seq_hint), _ptr(ws),
+                                     nbytes if ws is not None else 0, stream))
+    return o
+
+
 # Fragment images of the K transform for kv_decode_append (fq_kv_transform_image_f16: 32 KB per layer at head_dim 128), by (device, transform):
 # [image, transform, event of the preparing launch, {"done", "streams"}]. Same protocol as the Kronecker images: the entry keeps the transform alive,
 # in-place updates miss (ver), another stream waits for the preparing launch once; under capture only an image known complete (images_ready())

@@ -674,6 +674,26 @@ int fq_kv_batch_decode_copies(int fp16_cache, void* o, const void* q, const void
                               int num_layers, int layer_idx, int num_heads, int copies, int page_size, int head_dim, int batch_size, int seq_hint,
                               void* workspace, int64_t workspace_bytes, void* stream);
 
+/* SEVERAL NEW TOKENS PER REQUEST (round 7): causal attention of the q_len = T tokens a step appended to every request (a speculative verify
+ * of T draft tokens, a follow-up prompt, a prompt fed in pieces) over the paged cache — FlashInfer's append / prefill attention with the mask
+ * aligned bottom-right (include/flashinfer/prefill.cuh). Request b's length L_b (kv_indptr / last_page_offset) already counts its T new rows;
+ * query token t (0-based) attends rows 0 .. L_b - T + t (precondition L_b >= T). The arithmetic is fq_kv_batch_decode_split's: k / v
+ * de-quantised as n * scale - zero (fp16_cache != 0: fp16 rows, kv_param unused), scores / sqrt(head_dim), fp32 throughout, fp16 out.
+ *   q: [batch_size, q_len, H, head_dim] fp16 with H = num_cache_heads / copies * q_group query heads; query head h reads cache head
+ *      (h / q_group) * copies. copies = 1, q_group = 1: multi-head attention (or the replicated layout read copy by copy); copies = 1,
+ *      q_group = g: a cache that holds the KV heads once (fq_kv_batch_decode_gqa); copies = q_group = g: the reference's replicated layout
+ *      read one copy per group (fq_kv_batch_decode_copies). q_group a multiple of copies.
+ *   o: the same shape, or [batch_size, q_len, head_dim, H] with transpose_out != 0; q_trans [head_dim, head_dim] or NULL: the query is
+ *      q' = fp16(q . q_trans) inside the launch.
+ *   head_dim 128 (64: FQ_EUNSUPPORTED); any page_size; q_len < 1 or bad head arithmetic: FQ_EINVAL.
+ *   workspace: fq_kv_extend_workspace_bytes(batch_size, H, q_len, head_dim) bytes (0: never split) — the contract of fq_kv_batch_decode_split:
+ *   16-byte aligned, zeroed once, used by one launch at a time and for ONE geometry; NULL: no split. seq_hint as there. */
+int64_t fq_kv_extend_workspace_bytes(int batch_size, int num_q_heads, int q_len, int head_dim);
+int fq_kv_batch_extend(int fp16_cache, void* o, const void* q, const void* q_trans, int transpose_out, const void* kv_data,
+                       const void* kv_param, const void* kv_indptr, const void* kv_indices, const void* last_page_offset, int num_layers,
+                       int layer_idx, int num_cache_heads, int q_group, int copies, int q_len, int page_size, int head_dim, int batch_size,
+                       int seq_hint, void* workspace, int64_t workspace_bytes, void* stream);
+
 /*
  * The fp16 configuration of the same cache (MultiLayerPagedKVCache4Bit(disable_quant=True), kv_cache.py:177-190;
  * init_kv_f16 / append_kv_f16 / batch_decode_f16, kv_cache.py:107-137): kv_data [pages, num_layers, 2, num_heads, page_size,
