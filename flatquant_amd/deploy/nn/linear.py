@@ -58,6 +58,7 @@ class Linear4bit(torch.nn.Module):
             self.register_buffer("bias", torch.zeros((self.out_features), dtype=dtype))
         else:
             self.bias = None
+        ops.invalidate_on_load(self)   # weights loaded later (into inference tensors: no version counter moves): no stale operand images
 
     def _weight_image(self):
         """BF6 operand image of ``weight`` for the FP6 matrix path (csrc/fq_gemm_bf6.hip), rebuilt when the buffer is
@@ -67,7 +68,7 @@ class Linear4bit(torch.nn.Module):
             return None
         if self.out_features < self.fp6_min_out_features:
             return None
-        key = (self.weight.data_ptr(), ops.ver(self.weight), self.weight.device)
+        key = (self.weight.data_ptr(), ops.ver(self.weight), self.weight.device, ops.cache_epoch())   # (the epoch: an in-place reload of an inference tensor, or through .data, has no version to show — ops.invalidate_caches())
         if getattr(self, "_wimg_key", None) != key:
             self._drop_wimg()
             need = int(ops.lib.fq_bf6_blob_bytes(self.out_features, self.in_features))   # 0.75 B/param (rows padded to 32) on top of the 0.5 B/param of `weight`
@@ -103,7 +104,7 @@ class Linear4bit(torch.nn.Module):
         fp32 unless the model was built under a fp16 default dtype, and a conversion launch per call costs more than the
         decode-sized GEMM itself."""
         b = self.bias
-        key = (self.weight_scales.data_ptr(), ops.ver(self.weight_scales), None if b is None else (b.data_ptr(), ops.ver(b)))
+        key = (self.weight_scales.data_ptr(), ops.ver(self.weight_scales), None if b is None else (b.data_ptr(), ops.ver(b)), ops.cache_epoch())
         if getattr(self, "_s16_key", None) != key:
             self._s16 = (self.weight_scales.reshape(-1).to(torch.float16).contiguous(),
                          None if b is None else b.to(torch.float16).contiguous())
@@ -115,7 +116,7 @@ class Linear4bit(torch.nn.Module):
         FP6 image. ``decode_image = False`` turns the path off."""
         if not self.decode_image or self.in_features % 64:
             return None
-        key = (self.weight.data_ptr(), ops.ver(self.weight), self.weight.device)
+        key = (self.weight.data_ptr(), ops.ver(self.weight), self.weight.device, ops.cache_epoch())   # (the epoch: an in-place reload of an inference tensor, or through .data, has no version to show — ops.invalidate_caches())
         if getattr(self, "_dimg_key", None) != key:
             self._dimg = ops.int4_to_frag(self.weight)
             self._dimg_key = key

@@ -6,9 +6,19 @@ tensors — here one launch per tensor (fq_kv_quant_f16) instead of a GEMM plus 
 cache itself and the INT4 decode attention (init_kv_i4 / append_kv_i4 / batch_decode_i4, kernels/flashinfer.cu) are
 outside this round's scope; these functions produce exactly the tensors those entry points take.
 """
+import contextlib
+import itertools
+
 import torch
 
 from ... import ops
+
+_SERIAL = itertools.count(1)    # MultiLayerPagedKVCache4Bit.serial: never handed out twice in a process (id() is, as soon as an object dies)
+
+
+def _capturing(t: torch.Tensor) -> bool:
+    """Is the current stream of ``t``'s device recording a graph? (Only ever asked of a device that exists: a CPU cache never is.)"""
+    return t.is_cuda and torch.cuda.is_current_stream_capturing()
 
 
 def _clip(v) -> float:
@@ -147,6 +157,7 @@ class MultiLayerPagedKVCache4Bit:
         self.read_one_copy = bool(read_one_copy)
         self._pending = None    # a decode step's (k, v, transform, index tensors, layer) not yet appended: the closure's launch will (fuse_append)
         self.length = 0
+        self.serial = next(_SERIAL)   # deploy.graphed keys its captured graphs by this, never by id(): a new cache allocated where a dropped one lay is another cache
         self.generation = 0     # bumped when the page / index storage moves: graphs captured over the old pointers are stale (deploy.graphed)
         self._log = None        # deploy.graphed: the (layer_idx, added) host steps of the calls made while it is a list
         self._skip_host = False  # deploy.graphed: update() leaves the host step to replay_host() (capture pass)
@@ -251,8 +262,39 @@ class MultiLayerPagedKVCache4Bit:
         return {"kv_data": self._pages, "kv_param": self._scales, "kv_indptr": st["indptr"],
                 "kv_indices": st["indices"][:bsz * page_cnt], "last_page_offset": st["last"]}
 
+    def graph_addresses(self):
+        """The device addresses a captured decode step of this cache holds as constants (deploy.graphed compares them before every replay):
+        the pages, the scales and the static index tensors. Host reads only."""
+        st = self.__dict__.get("_st")
+        return (self._pages.data_ptr(), self._scales.data_ptr(),
+                None if st is None else (st["indptr"].data_ptr(), st["indices"].data_ptr(), st["last"].data_ptr()))
+
+    def _refuse_capture(self):
+        """The host side of a step (the length, the index tensors' contents) must not run while a graph is being recorded: it would happen
+        ONCE, its fills and copies would become nodes with capture-time constants, and every replay would write the new token to the same
+        slot and attend over the same length. deploy.GraphedDecode runs it outside the capture (``replay_host``) and sets ``_skip_host``."""
+        if not self._skip_host and _capturing(self._pages):
+            raise RuntimeError("MultiLayerPagedKVCache4Bit.update() under stream capture: the cache's host step (length, page indices) "
+                               "would be frozen into the graph. Wrap the step in deploy.GraphedDecode (deploy.fuse(model, capture=True)) "
+                               "and pass the cache as an argument; it applies the host step outside the capture.")
+
+    @contextlib.contextmanager
+    def host_side_done(self):
+        """For a HAND-WRITTEN capture of a step at a fixed length (the benchmarks' graphs, which replay one and the same step): inside this block
+        ``update`` leaves the length and the index tensors as the last eager step set them and only issues its launches. Whoever replays
+        such a graph for successive tokens calls ``replay_host`` before each replay — or uses deploy.GraphedDecode, which does."""
+        self._skip_host = True
+        try:
+            yield self
+        finally:
+            self._skip_host = False
+
     def _host_step(self, layer_idx, added, mask=None):
         """The host side of one ``update``: layer 0 makes room and advances the length; the index tensors follow the length."""
+        self._refuse_capture()
+        self._advance(layer_idx, added, mask)
+
+    def _advance(self, layer_idx, added, mask=None):
         if layer_idx == 0:
             self._ensure_page_cnt_per_batch(self.page_cnt_from_length(self.length + added))
             self.length += added
@@ -261,11 +303,14 @@ class MultiLayerPagedKVCache4Bit:
             self._specs = self._static_specs() if mask is None else self.get_cache_specs_for_flash_infer(mask)
             self._specs_key = key
 
-    def replay_host(self, log):
+    def replay_host(self, log, checked=True):
         """deploy.graphed: apply the host steps ``log`` recorded ([(layer_idx, added), ...]) — what the update() calls inside a captured
-        decode step did on the host — before the graph that holds their launches is replayed."""
+        decode step did on the host — before the graph that holds their launches is replayed. ``checked=False``: the caller has looked at
+        the stream itself (GraphedDecode.__call__ does, first thing)."""
+        if checked:
+            self._refuse_capture()
         for layer_idx, added in log:
-            self._host_step(layer_idx, added)
+            self._advance(layer_idx, added)
 
     def _as_f16(self, t):
         """``t`` as a contiguous fp16 tensor on the cache's device — itself when it already is one; otherwise ONE converted copy per source tensor
@@ -340,6 +385,7 @@ class MultiLayerPagedKVCache4Bit:
         return attend
 
     def update(self, key_states, value_states, layer_idx, cache_kwargs=None):
+        self._refuse_capture()
         self._flush_pending()
         cache_kwargs = cache_kwargs or {}
         mask = cache_kwargs.get("attention_mask")
@@ -352,7 +398,7 @@ class MultiLayerPagedKVCache4Bit:
         if self._log is not None:
             self._log.append((layer_idx, added) if (mask is None and not self._needs_init[layer_idx]) else None)   # None: not replayable
         if not self._skip_host:
-            self._host_step(layer_idx, added, mask)
+            self._advance(layer_idx, added, mask)        # (_host_step without its second look at the stream)
         specs = self._specs
         args = (specs["kv_data"], specs["kv_param"], specs["kv_indptr"], specs["kv_indices"], specs["last_page_offset"])
         tk16 = self._as_f16(tk)

@@ -164,9 +164,8 @@ def main():
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
-            step(x)
-            cache.length -= 1
-            with torch.cuda.graph(graph, stream=s):
+            step(x)                             # (the host side of the captured step: the length and index tensors it leaves are the graph's)
+            with cache.host_side_done(), torch.cuda.graph(graph, stream=s):
                 step(x)
             cache.length -= 1
         torch.cuda.synchronize()
@@ -231,9 +230,8 @@ def main():
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(s):
-        step(x)
-        cache.length -= 1
-        with torch.cuda.graph(graph, stream=s):
+        step(x)                                 # (the host side of the captured step: the length and index tensors it leaves are the graph's)
+        with cache.host_side_done(), torch.cuda.graph(graph, stream=s):
             y = step(x)
         cache.length -= 1
     torch.cuda.synchronize()
