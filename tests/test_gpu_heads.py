@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from oracle import fq_oracle as O
+from tests import guards
 from tests.conftest import same_bits
 
 pytestmark = pytest.mark.gpu
@@ -137,12 +138,18 @@ def test_block_dyadic_bit_exact_and_no_out_of_bounds(ops, H, hd):
     guard[1:-1] = dev(x)
     xin = guard[1:-1]
     for tr in (True, False):
-        o = ops.block_quant(xin, dev(Pm), [(0.982, 0.9)], P_ | NC0 | T | F, transpose_out=tr)
-        ref = O.block_quant(x, Pm, 0.982, 0.9, transpose_out=tr, clamp0=False)
-        assert np.array_equal(host(o.y).reshape(rows, -1), ref["y16"])
-        assert np.array_equal(host(o.q[0]), ref["packed"])
-        assert np.array_equal(host(o.scale[0]), ref["scale16"])
-        assert same_bits(host(o.fq[0]).reshape(rows, -1), ref["fq"])
+        for poison in guards.POISONS:         # the outputs are allocated between canaries (tests/guards.py), once per poison byte
+            g = guards.Guard(poison)
+            with g.on(ops):
+                o = ops.block_quant(xin, g.guard_input(dev(Pm)), [(0.982, 0.9)], P_ | NC0 | T | F, transpose_out=tr)
+                torch.cuda.synchronize()
+            g.check()
+            assert len(g.find("empty")) == 4
+            ref = O.block_quant(x, Pm, 0.982, 0.9, transpose_out=tr, clamp0=False)
+            assert np.array_equal(host(o.y).reshape(rows, -1), ref["y16"])
+            assert np.array_equal(host(o.q[0]), ref["packed"])
+            assert np.array_equal(host(o.scale[0]), ref["scale16"])
+            assert same_bits(host(o.fq[0]).reshape(rows, -1), ref["fq"])
 
 
 def test_block_refuses_what_it_cannot_run(ops):
