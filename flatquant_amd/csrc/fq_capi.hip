@@ -64,7 +64,10 @@ int fq_launch_kv_append(void* kv_data, void* kv_param, const int* indptr, const 
 int fq_launch_kv_decode(f16* o, const f16* q, void* kv_data, void* kv_param, const int* indptr, const int* indices, const int* last,
                         int num_layers, int layer_idx, int num_heads, int page_size, int head_dim, int batch, const f16* qt,
                         int transpose_out, hipStream_t stream, bool f16_cache = false, float* ws = nullptr, int splits = 1, int qgroup = 1,
-                        const f16* k_new = nullptr, const f16* v_new = nullptr, const void* t_image = nullptr, int src_heads = 1, int copies = 1);
+                        const f16* k_new = nullptr, const f16* v_new = nullptr, const void* t_image = nullptr, int src_heads = 1, int copies = 1,
+                        const f16* rope_cos = nullptr, const f16* rope_sin = nullptr);
+int fq_launch_rope(f16* q_out, f16* k_out, const f16* q, const f16* k, const f16* cos, const f16* sin, int64_t tokens, int q_heads, int k_heads,
+                   int head_dim, hipStream_t stream);
 int64_t fq_kv_timage_bytes(int hd);
 int fq_launch_kv_timage(const f16* T, int hd, void* img, hipStream_t stream);
 int fq_kv_decode_splits(int batch, int num_heads, int seq_hint);
@@ -1267,11 +1270,12 @@ int fq_kv_transform_image_f16(const void* trans, int head_dim, void* image, void
     return check_launch(fq_launch_kv_timage((const f16*)trans, head_dim, image, (hipStream_t)stream), "fq_kv_transform_image_f16");
 }
 
-int fq_kv_decode_append_i4(void* o, const void* q, const void* q_trans, int transpose_out, const void* k_new, const void* v_new,
-                           const void* k_trans_image, int src_heads, const void* kv_data, const void* kv_param, const void* kv_indptr,
-                           const void* kv_indices, const void* last_page_offset, int num_layers, int layer_idx, int num_kv_heads, int q_group,
-                           int page_size, int head_dim, int batch_size, int seq_hint, int read_one_copy, void* workspace, int64_t workspace_bytes, void* stream) {
-    const char* what = "fq_kv_decode_append_i4";
+// fq_kv_decode_append_i4 and fq_kv_decode_append_rope_i4 (cos / sin: the step's rotary tables, both or neither)
+static int kv_decode_append(const char* what, void* o, const void* q, const void* q_trans, int transpose_out, const void* k_new, const void* v_new,
+                            const void* k_trans_image, int src_heads, const void* kv_data, const void* kv_param, const void* kv_indptr,
+                            const void* kv_indices, const void* last_page_offset, int num_layers, int layer_idx, int num_kv_heads, int q_group,
+                            int page_size, int head_dim, int batch_size, int seq_hint, int read_one_copy, void* workspace, int64_t workspace_bytes, void* stream,
+                            const void* cos, const void* sin) {
     int rc = kv_geometry_ok(what, num_layers, layer_idx, num_kv_heads, page_size, head_dim, batch_size);
     if (rc != FQ_OK) return rc;
     if (q_group < 1 || q_group > 64) return fail(FQ_EINVAL, "%s: q_group=%d out of [1, 64]", what, q_group);
@@ -1281,6 +1285,8 @@ int fq_kv_decode_append_i4(void* o, const void* q, const void* q_trans, int tran
     if (!o || !q || !k_new || !v_new || !kv_data || !kv_param || !kv_indptr || !kv_indices || !last_page_offset)
         return fail(FQ_EINVAL, "%s: NULL pointer", what);
     FQ_NEED_ALIGN16(what, kv_data, q_trans, workspace, k_new, v_new, k_trans_image);
+    if ((cos != nullptr) != (sin != nullptr)) return fail(FQ_EINVAL, "%s: cos and sin go together (both, or neither for no rotary embedding)", what);
+    FQ_NEED_ALIGN16(what, cos, sin);
     const int q_heads = num_kv_heads * q_group;
     // read_one_copy: the num_kv_heads / src_heads cache heads of a source head hold identical rows (this function and fq_kv_quant_append_i4 write
     // them so): the launch reads the first copy for the whole group of query heads (and still writes the new row to every copy)
@@ -1293,8 +1299,44 @@ int fq_kv_decode_append_i4(void* o, const void* q, const void* q_trans, int tran
     rc = fq_launch_kv_decode((f16*)o, (const f16*)q, (void*)kv_data, (void*)kv_param, (const int*)kv_indptr, (const int*)kv_indices,
                              (const int*)last_page_offset, num_layers, layer_idx, q_heads, page_size, head_dim, batch_size,
                              (const f16*)q_trans, transpose_out != 0, (hipStream_t)stream, false, (float*)workspace, splits, share,
-                             (const f16*)k_new, (const f16*)v_new, k_trans_image, src_heads, copies);
+                             (const f16*)k_new, (const f16*)v_new, k_trans_image, src_heads, copies, (const f16*)cos, (const f16*)sin);
     return check_launch(rc, what);
+}
+
+int fq_kv_decode_append_i4(void* o, const void* q, const void* q_trans, int transpose_out, const void* k_new, const void* v_new,
+                           const void* k_trans_image, int src_heads, const void* kv_data, const void* kv_param, const void* kv_indptr,
+                           const void* kv_indices, const void* last_page_offset, int num_layers, int layer_idx, int num_kv_heads, int q_group,
+                           int page_size, int head_dim, int batch_size, int seq_hint, int read_one_copy, void* workspace, int64_t workspace_bytes, void* stream) {
+    return kv_decode_append("fq_kv_decode_append_i4", o, q, q_trans, transpose_out, k_new, v_new, k_trans_image, src_heads, kv_data, kv_param, kv_indptr,
+                            kv_indices, last_page_offset, num_layers, layer_idx, num_kv_heads, q_group, page_size, head_dim, batch_size, seq_hint,
+                            read_one_copy, workspace, workspace_bytes, stream, nullptr, nullptr);
+}
+
+int fq_kv_decode_append_rope_i4(void* o, const void* q, const void* q_trans, int transpose_out, const void* k_new, const void* v_new,
+                                const void* k_trans_image, int src_heads, const void* kv_data, const void* kv_param, const void* kv_indptr,
+                                const void* kv_indices, const void* last_page_offset, int num_layers, int layer_idx, int num_kv_heads, int q_group,
+                                int page_size, int head_dim, int batch_size, int seq_hint, int read_one_copy, void* workspace, int64_t workspace_bytes,
+                                void* stream, const void* cos, const void* sin) {
+    return kv_decode_append("fq_kv_decode_append_rope_i4", o, q, q_trans, transpose_out, k_new, v_new, k_trans_image, src_heads, kv_data, kv_param, kv_indptr,
+                            kv_indices, last_page_offset, num_layers, layer_idx, num_kv_heads, q_group, page_size, head_dim, batch_size, seq_hint,
+                            read_one_copy, workspace, workspace_bytes, stream, cos, sin);
+}
+
+int fq_rope_f16(void* q_out, void* k_out, const void* q, const void* k, const void* cos, const void* sin, int64_t tokens, int q_heads, int k_heads,
+                int head_dim, int rotary_dim, void* stream) {
+    const char* what = "fq_rope_f16";
+    if (head_dim != 64 && head_dim != 128) return fail(FQ_EUNSUPPORTED, "%s: head_dim=%d must be 64 or 128", what, head_dim);
+    if (rotary_dim != head_dim) return fail(FQ_EUNSUPPORTED, "%s: rotary_dim=%d: only the whole head (head_dim=%d) is rotated, no partial rotary", what, rotary_dim, head_dim);
+    if (!q && !k) return fail(FQ_EINVAL, "%s: q and k are both NULL", what);
+    if (tokens < 0 || (q && (q_heads < 1 || !q_out)) || (k && (k_heads < 1 || !k_out)) || !cos || !sin)
+        return fail(FQ_EINVAL, "%s: tokens=%lld, q_heads=%d, k_heads=%d: every tensor given needs its output, a head count >= 1, and cos / sin", what,
+                    (long long)tokens, q_heads, k_heads);
+    FQ_NEED_ALIGN16(what, q_out, k_out, q, k, cos, sin);
+    const int64_t heads = (q ? q_heads : 0) + (int64_t)(k ? k_heads : 0);
+    if (tokens > 0x7FFFFFFF || heads > 65535) return fail(FQ_EINVAL, "%s: tokens=%lld x %lld heads is more than one launch takes", what, (long long)tokens, (long long)heads);
+    if (tokens == 0) return FQ_OK;
+    return check_launch(fq_launch_rope((f16*)q_out, (f16*)k_out, (const f16*)q, (const f16*)k, (const f16*)cos, (const f16*)sin, tokens, q ? q_heads : 0,
+                                       k ? k_heads : 0, head_dim, (hipStream_t)stream), what);
 }
 
 int fq_kv_batch_decode_copies(int fp16_cache, void* o, const void* q, const void* q_trans, int transpose_out, const void* kv_data,

@@ -16,6 +16,22 @@ __device__ __forceinline__ f16 xchg32(f16 v, int lane) {  // value of lane ^ 32
     return __builtin_bit_cast(f16, (unsigned short)r);
 }
 
+// Rotary position embedding as transformers' apply_rotary_pos_emb computes it on fp16 tensors: out = rn16(rn16(x cos) + rn16(r sin)) with r the
+// rotate_half partner of x (- x[j + hd / 2] in the first half of the features, x[j - hd / 2] in the second). THREE fp16 roundings: a fused
+// multiply-add (one rounding less) differs in about three elements of ten, so the contraction is switched off here whatever the file is built with.
+__device__ __forceinline__ f16 kv_rope1(f16 x, f16 r, f16 c, f16 s) {
+#pragma clang fp contract(off)
+    const f16 a = x * c;
+    const f16 b = r * s;
+    return a + b;
+}
+__device__ __forceinline__ f16x8 kv_rope8(f16x8 x, f16x8 r, f16x8 c, f16x8 s) {
+#pragma clang fp contract(off)
+    const f16x8 a = x * c;
+    const f16x8 b = r * s;
+    return a + b;
+}
+
 struct KvParams {
     f16 scale, zero;
 };

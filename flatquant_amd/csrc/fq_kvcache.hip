@@ -48,6 +48,8 @@ struct KvNew {
     const f16* v;        // ... values
     const uint4* timg;   // the K transform as the fragment image fq_kv_transform_image_f16 wrote (32 KB at head_dim 128), or nullptr: no transform
     int src_heads;       // heads of k / v: cache head c is a copy of source head c / (cache heads / src_heads) (kv_cache.py:286-296)
+    const f16* cos;      // [batch, head_dim] fp16 rotary tables of the step (fq_kv_decode_append_rope_i4), or nullptr: no rotary embedding. With them the
+    const f16* sin;      // launch rotates its queries and the new K row first (fqkv::kv_rope1: the three fp16 roundings of apply_rotary_pos_emb); V never
 };
 
 struct PagedKv {
@@ -193,9 +195,14 @@ __device__ __forceinline__ float* kv_states(float* ws, size_t pairs) { return ws
 #define KV_PVM_WIDE_MAX 512    // the merged matrix-pipe launch runs eight-wave workgroups up to this many of them (two per CU); beyond, four-wave workgroups, four per CU:
                                // the step at 80 / 96 / 128 requests 164.5 / 172.0 / 210.8 -> 159.4 / 168.1 / 206.5 us against a bound of 1024 (r06c75)
 #endif
-template <int HD, int NW, bool UNI, bool F16, bool SPLIT, int QG = 1, bool APPEND = false>
-__global__ __launch_bounds__(NW * 64, (KV_PVM_OCC4 && KV_PV_MFMA && QG == 4 && !F16 && UNI) ? 4 : 2) void fq_kv_decode_kernel(f16* __restrict__ o, const f16* __restrict__ q, PagedKv p,
+// APPEND: 0 the plain decode launch, 1 with the step's own row (KvNew), 2 (round 8) that with the step's rotary embedding in front — a template
+// value and not a runtime pointer of the APPEND instantiations: as a pointer it cost those up to nine VGPRs and two SGPRs; so every instantiation
+// that was there before keeps its code, registers and spills. The four-head form with rotary embedding is NOT held to 128 VGPRs (132, three waves
+// per SIMD): held, it spills four to five registers like its siblings, and nothing new may spill (tests/test_host_cpu.py).
+template <int HD, int NW, bool UNI, bool F16, bool SPLIT, int QG = 1, int APPEND = 0>
+__global__ __launch_bounds__(NW * 64, (KV_PVM_OCC4 && KV_PV_MFMA && QG == 4 && !F16 && UNI && APPEND != 2) ? 4 : 2) void fq_kv_decode_kernel(f16* __restrict__ o, const f16* __restrict__ q, PagedKv p,
                                                                const f16* __restrict__ qt, int transpose_out, float* ws, int qgroup, KvNew nw) {
+    constexpr bool ROPE = APPEND == 2;
     constexpr int QL = HD / 32;        // lanes per cached row: 4 for head_dim 128, 2 for 64
     constexpr int RPW = 64 / QL;       // rows per wave and step: the N of the MFMA (16 / 32)
     constexpr int NS = NW * RPW;       // partial softmax states per workgroup
@@ -219,6 +226,36 @@ __global__ __launch_bounds__(NW * 64, (KV_PVM_OCC4 && KV_PV_MFMA && QG == 4 && !
     const int pg0 = p.indptr[b], pg1 = p.indptr[b + 1];
     const int64_t seq_len = (int64_t)(pg1 - pg0 - 1) * p.page_size + p.last_page_offset[b];
 
+    constexpr size_t NEW_OFF = (sizeof(float) * ((size_t)NS * (HD + 1 + 2) + QG * HD + NS + NW + (size_t)(NW * 64 / HD) * (HD + 2)) + 15) & ~(size_t)15;
+    // ROPE (fq_kv_decode_append_rope_i4): the workgroup's QG queries and the new K row of its cache head are rotated ONCE, element by element — feature j with its partner
+    // j +- HD / 2 under cos[j] / sin[j] — before anything else looks at them: the queries land in s_q as the fp16 values the standalone launch
+    // would have stored (the transform below then reads them there instead of q), the K row in s_krot for the APPEND prologue.
+    // Only a workgroup whose rows include the request's last row (`own` below) needs the K row. The K row is rotated here, from global memory
+    // through LDS, and not lane-locally in the APPEND prologue: there a lane would hold the row, cos and sin (96 registers) next to the transform.
+    f16* s_krot = reinterpret_cast<f16*>(kv_smem + NEW_OFF + 256);
+    if constexpr (ROPE) {
+        const bool own_k = seq_len > 0 && (!SPLIT || (int)((((seq_len - 1) / RPW) % ((int)gridDim.z * NW)) / NW) == (int)blockIdx.z);
+        const f16* cs = nw.cos + (size_t)b * HD;
+        const f16* sn = nw.sin + (size_t)b * HD;
+        const f16* q0 = q + ((size_t)b * QH + head) * HD;
+        const f16* k0 = nw.k + ((size_t)b * nw.src_heads + chead / (p.num_heads / nw.src_heads)) * HD;
+        for (int idx = tid; idx < (own_k ? QG + 1 : QG) * HD; idx += NW * 64) {
+            const int g = idx / HD, j = idx % HD;
+            const f16* src = g < QG ? q0 + g * HD : k0;
+            const f16 x = src[j], xp = src[j ^ (HD / 2)];
+            const f16 y = fqkv::kv_rope1(x, j < HD / 2 ? -xp : xp, cs[j], sn[j]);
+            if (g < QG) s_q[idx] = (float)y;
+            else s_krot[j] = y;
+        }
+        __syncthreads();
+    }
+    // the query value the transform below multiplies: q itself, or (ROPE) the rotated one s_q holds — every read of s_q lies in front of the
+    // barrier its new contents are written behind
+    auto q_at = [&](const f16* row, int g, int i) -> float {
+        if constexpr (ROPE) return s_q[g * HD + i];
+        else return (float)row[(size_t)g * HD + i];
+    };
+
     // the query as fp16 values in LDS: q itself, or q' = fp16(q . qt) (kv_cache.py:139-140: torch.matmul(q.half(),
     // trans_matrix_k_inv_t)), fp32 accumulation — every thread sums HD / NCHQ terms of one output feature (one thread per feature
     // walked all HD terms in a dependent chain: microseconds in front of every workgroup, and a split launch has many), the NCHQ
@@ -239,7 +276,7 @@ __global__ __launch_bounds__(NW * 64, (KV_PVM_OCC4 && KV_PV_MFMA && QG == 4 && !
         for (int i = c * CHQ; i < (c + 1) * CHQ; ++i) {
             const float t = (float)qt[i * HD + j];
 #pragma unroll
-            for (int g = 0; g < QG; ++g) a[g] = __builtin_fmaf((float)qrow0[(size_t)g * HD + i], t, a[g]);
+            for (int g = 0; g < QG; ++g) a[g] = __builtin_fmaf(q_at(qrow0, g, i), t, a[g]);
         }
 #pragma unroll
         for (int g = 0; g < QG; ++g) s_o[g * NCHQ + c][j] = a[g];
@@ -261,7 +298,7 @@ __global__ __launch_bounds__(NW * 64, (KV_PVM_OCC4 && KV_PV_MFMA && QG == 4 && !
             const int j = tid % HD, c = tid / HD;
             float a = 0.0f;
 #pragma unroll 8
-            for (int i = c * CHQ; i < (c + 1) * CHQ; ++i) a = __builtin_fmaf((float)qrow[i], (float)qt[i * HD + j], a);
+            for (int i = c * CHQ; i < (c + 1) * CHQ; ++i) a = __builtin_fmaf(ROPE ? s_q[g * HD + i] : (float)qrow[i], (float)qt[i * HD + j], a);
             s_o[c][j] = a;
             __syncthreads();
             if (tid < HD) {
@@ -270,7 +307,7 @@ __global__ __launch_bounds__(NW * 64, (KV_PVM_OCC4 && KV_PV_MFMA && QG == 4 && !
                 for (int cc = 0; cc < NCHQ; ++cc) t += s_o[cc][tid];
                 s_q[g * HD + tid] = (float)(f16)t;
             }
-        } else {
+        } else if (!ROPE) {     // (ROPE: s_q holds the rotated query already)
             for (int j = tid; j < HD; j += NW * 64) s_q[g * HD + j] = (float)qrow[j];
         }
         __syncthreads();
@@ -304,7 +341,7 @@ __global__ __launch_bounds__(NW * 64, (KV_PVM_OCC4 && KV_PV_MFMA && QG == 4 && !
 
     // APPEND: the new row (see KvNew). s_new (behind every other LDS array): [0..15] the K row's dwords, [16..31] the V row's, [32] / [33] the
     // (scale, zero) pairs, [36..] the per-wave extrema of the prologue.
-    constexpr size_t NEW_OFF = (sizeof(float) * ((size_t)NS * (HD + 1 + 2) + QG * HD + NS + NW + (size_t)(NW * 64 / HD) * (HD + 2)) + 15) & ~(size_t)15;
+    // With rotary tables: [64..127] the rotated K row (s_krot above).
     uint32_t* s_new = reinterpret_cast<uint32_t*>(kv_smem + NEW_OFF);
     const int64_t last_row = seq_len - 1;
     bool own = false;    // (workgroup-uniform) this workgroup's rows include last_row
@@ -327,7 +364,11 @@ __global__ __launch_bounds__(NW * 64, (KV_PVM_OCC4 && KV_PV_MFMA && QG == 4 && !
 #pragma unroll
                     for (int s = 0; s < 8; ++s) {
                         tf[s] = __builtin_bit_cast(f16x8, nw.timg[(s * 4 + wave) * 64 + lane]);
-                        xf[s] = __builtin_bit_cast(f16x8, reinterpret_cast<const uint4*>(krow)[2 * s + h]);
+                        if (!ROPE) xf[s] = __builtin_bit_cast(f16x8, reinterpret_cast<const uint4*>(krow)[2 * s + h]);
+                    }
+                    if (ROPE) {
+#pragma unroll
+                        for (int s = 0; s < 8; ++s) xf[s] = __builtin_bit_cast(f16x8, reinterpret_cast<const uint4*>(s_krot)[2 * s + h]);
                     }
                     f32x16 a = {0};
 #pragma unroll
@@ -335,8 +376,14 @@ __global__ __launch_bounds__(NW * 64, (KV_PVM_OCC4 && KV_PV_MFMA && QG == 4 && !
 #pragma unroll
                     for (int r = 0; r < 16; ++r) kv16[0][r] = (f16)a[r];
                 } else {
-                    const f16x8 k0 = __builtin_bit_cast(f16x8, reinterpret_cast<const uint4*>(krow + wave * 32 + 16 * h)[0]);
-                    const f16x8 k1 = __builtin_bit_cast(f16x8, reinterpret_cast<const uint4*>(krow + wave * 32 + 16 * h)[1]);
+                    f16x8 k0, k1;
+                    if (ROPE) {
+                        k0 = __builtin_bit_cast(f16x8, reinterpret_cast<const uint4*>(s_krot + wave * 32 + 16 * h)[0]);
+                        k1 = __builtin_bit_cast(f16x8, reinterpret_cast<const uint4*>(s_krot + wave * 32 + 16 * h)[1]);
+                    } else {
+                        k0 = __builtin_bit_cast(f16x8, reinterpret_cast<const uint4*>(krow + wave * 32 + 16 * h)[0]);
+                        k1 = __builtin_bit_cast(f16x8, reinterpret_cast<const uint4*>(krow + wave * 32 + 16 * h)[1]);
+                    }
 #pragma unroll
                     for (int r = 0; r < 8; ++r) kv16[0][r] = k0[r], kv16[0][8 + r] = k1[r];
                 }
@@ -981,7 +1028,7 @@ int64_t fq_kv_decode_ws_bytes(int batch, int num_heads, int head_dim) {   // for
 int fq_launch_kv_decode(f16* o, const f16* q, void* kv_data, void* kv_param, const int* indptr, const int* indices, const int* last,
                         int num_layers, int layer_idx, int num_heads, int page_size, int head_dim, int batch, const f16* qt,
                         int transpose_out, hipStream_t stream, bool f16_cache, float* ws, int splits, int qgroup, const f16* k_new,
-                        const f16* v_new, const void* t_image, int src_heads, int copies) {
+                        const f16* v_new, const void* t_image, int src_heads, int copies, const f16* rope_cos, const f16* rope_sin) {
     // num_heads: QUERY heads (q, o); qgroup of them share one set of rows; the cache holds (num_heads / qgroup) * copies heads: copies = 1 and
     // qgroup = 1 the reference's layout read head by head, copies = 1 and qgroup = g a cache that holds the KV heads once, copies = qgroup = g the
     // reference's layout (g identical copies per KV head) read ONE copy per group
@@ -990,7 +1037,9 @@ int fq_launch_kv_decode(f16* o, const f16* q, void* kv_data, void* kv_param, con
     p.copies = copies;
     const bool split = ws != nullptr && splits > 1;
     // k_new: the step's own row is quantised and appended by this launch (KvNew): INT4 cache, head_dim 128, page_size % 16 == 0 only
-    KvNew nw = {k_new, v_new, reinterpret_cast<const uint4*>(t_image), src_heads};
+    // rope_cos / rope_sin [batch, head_dim]: that launch rotates its queries and the new K row first (fq_kv_decode_append_rope_i4)
+    if ((rope_cos != nullptr) != (rope_sin != nullptr) || (rope_cos != nullptr && k_new == nullptr)) return -1000;
+    KvNew nw = {k_new, v_new, reinterpret_cast<const uint4*>(t_image), src_heads, rope_cos, rope_sin};
     if (k_new != nullptr && (f16_cache || head_dim != 128 || page_size % 16 || v_new == nullptr || src_heads < 1 || (num_heads / qgroup * copies) % src_heads)) return -1000;
     const bool append = k_new != nullptr;
     // (round 6) a shared cache with 2 or 4 query heads per KV head at head_dim 128: ONE workgroup per (request, KV head) serves its query heads
@@ -1002,15 +1051,15 @@ int fq_launch_kv_decode(f16* o, const f16* q, void* kv_data, void* kv_param, con
 #define FQ_DEC5(HD_, NW_, UNI_, F16_, SP_, QG_, AP_)                                                                   \
     {                                                                                                                 \
         constexpr size_t ns_ = (size_t)(NW_ * (64 / (HD_ / 32))), nch_ = (size_t)NW_ * 64 / HD_;                      \
-        constexpr size_t lds = sizeof(float) * (ns_ * (HD_ + 1 + 2) + QG_ * HD_ + ns_ + NW_ + nch_ + nch_ * (HD_ + 1)) + (AP_ ? 256 : 0); \
+        constexpr size_t lds = sizeof(float) * (ns_ * (HD_ + 1 + 2) + QG_ * HD_ + ns_ + NW_ + nch_ + nch_ * (HD_ + 1)) + (AP_ == 2 ? 512 : AP_ ? 256 : 0); \
         FQ_RAISE_LDS_CAP((fq_kv_decode_kernel<HD_, NW_, UNI_, F16_, SP_, QG_, AP_>), lds);                            \
         hipLaunchKernelGGL((fq_kv_decode_kernel<HD_, NW_, UNI_, F16_, SP_, QG_, AP_>), grid, dim3(NW_ * 64), lds, stream, o, q, p, qt, transpose_out, ws, qgroup, nw); \
     }
 #define FQ_DEC4(HD_, NW_, UNI_, F16_, SP_, QG_)                                                                        \
     {                                                                                                                 \
         if constexpr (HD_ == 128 && UNI_ && !F16_) {                                                                  \
-            if (append) FQ_DEC5(HD_, NW_, UNI_, F16_, SP_, QG_, true) else FQ_DEC5(HD_, NW_, UNI_, F16_, SP_, QG_, false) \
-        } else FQ_DEC5(HD_, NW_, UNI_, F16_, SP_, QG_, false)                                                         \
+            if (append && rope_cos != nullptr) FQ_DEC5(HD_, NW_, UNI_, F16_, SP_, QG_, 2) else if (append) FQ_DEC5(HD_, NW_, UNI_, F16_, SP_, QG_, 1) else FQ_DEC5(HD_, NW_, UNI_, F16_, SP_, QG_, 0) \
+        } else FQ_DEC5(HD_, NW_, UNI_, F16_, SP_, QG_, 0)                                                         \
     }
 #define FQ_DEC3(HD_, NW_, UNI_, F16_, SP_)                                                                             \
     {                                                                                                                 \

@@ -102,6 +102,15 @@ def n_q_is_cache_heads(kv_data, src_heads, group):
 # 66.5 -> 61.6 us at one request, 105 -> 99.5 at 16 (512 pairs), 162.6 -> 157.7 at 64 requests on the shared cache (512 pairs); level at 1024 and
 # 2048 pairs; 368 -> 373-379 at 4096 pairs (the prologue in front of every one of eight rounds of workgroups costs more than the launch it saves).
 FUSE_APPEND_MAX_PAIRS = 1024
+# rotate: up to this many (request, group of four query heads) PAIRS of the launch that serves four query heads per workgroup (groups of 4 / 8 from
+# 32 (request, KV head) pairs on) the decode launch also applies the rotary embedding; beyond, ONE ops.rope launch rotates the step's q and k in
+# front of it. Pairs, not workgroups: a split launch starts several workgroups per pair, but it splits only while the launch has at most ~256 of
+# them in all. The four-head kernel with rope is not held to 128 VGPRs (it would spill): 132, three waves per SIMD, so a CU holds one of its
+# eight-wave workgroups where the kernel without rope holds two. Measured on a Llama-3-8B layer's captured step with the rotation inside the
+# launch at every size (profiles/r08_rope_decode.txt, first table; none / in the launch / one launch in front): 98.0 / 97.2 / 99.9 us at 32
+# requests (256 pairs: one workgroup per CU either way), 125.1 / 136.1 / 127.5 at 64 (512), 195.7 / 203.2 / 199.3 at 128 (1024). With this
+# routing (second table there) rotate costs 3.1 / 5.6 us over no rope at 64 / 128 requests, 1.4 / 0.8 us above the one-launch form called directly. Launches of one or two query heads per workgroup keep their occupancy with rope and are not bounded here.
+ROPE_FUSE_MAX_FOUR_HEAD_WGS = 256
 
 
 class MultiLayerPagedKVCache4Bit:
@@ -120,7 +129,16 @@ class MultiLayerPagedKVCache4Bit:
     * ``cache_kwargs["attention_mask"]`` [bsz, seq] of 0 / 1 (ragged prompts, :315-326,362-372): the prompt tokens whose mask
       is 1 are compacted request by request into the cache; request lengths are the mask's row sums from then on (the mask
       grows by one column per decode step). As in the reference, all requests must need the same number of pages
-      (NotImplementedError otherwise, :371-372)."""
+      (NotImplementedError otherwise, :371-372).
+    * ``cache_kwargs["rotate"] = True`` (extension, round 8): the cache applies the rotary embedding itself, with the ``"cos"`` / ``"sin"``
+      [bsz, added, head_dim] the reference already passes in ``cache_kwargs`` (modeling_llama.py:113-118; ignored without the key): the caller
+      hands over UN-rotated keys and gives UN-rotated queries to the returned closure. Same pages, scales and outputs as rotating both with
+      transformers' ``apply_rotary_pos_emb`` first, byte for byte. A decode step on the fused-append route rotates inside its one launch
+      (ops.kv_decode_append(rope=...); beyond ROPE_FUSE_MAX_FOUR_HEAD_WGS workgroups of four query heads: one ops.rope launch for q and k
+      in front of it); every other route (``fuse_append=False``, more than FUSE_APPEND_MAX_PAIRS pairs, ``trans="had"`` — rope
+      comes before the rotation —, the fp16 configuration, several tokens per step, a ragged mask, the prompt) runs ops.rope on the keys in
+      ``update`` and on the queries in the closure, then the usual launches. The PROMPT's queries are the caller's to rotate
+      (deploy.functional.apply_rotary_pos_emb): the first call returns states, not a closure."""
 
     def __init__(self, batch_size, page_size, max_seq_len, device, n_layers, num_heads, head_dim, disable_quant=False,
                  trans_dtype=torch.float16, trans="had", group_size=1, share_kv_heads=False, fuse_append=True,
@@ -142,6 +160,7 @@ class MultiLayerPagedKVCache4Bit:
         self.page_size, self.batch_size, self.max_seq_len = page_size, batch_size, max_seq_len
         self.device, self.n_layers, self.trans, self.group_size = device, n_layers, trans, group_size
         self.share_kv_heads = bool(share_kv_heads) and group_size > 1
+        self._shared_group = group_size if self.share_kv_heads else 1      # query heads per cache head of the shared layout
         if self.share_kv_heads:
             assert num_heads % group_size == 0
             num_heads = num_heads // group_size          # heads the pages hold
@@ -335,7 +354,9 @@ class MultiLayerPagedKVCache4Bit:
         """Append the rows a decode step left to its closure's launch if that closure was never called (the two-launch form's first launch)."""
         pend, self._pending = self._pending, None
         if pend is not None:
-            k, v, tk16, args, layer_idx, group = pend
+            k, v, tk16, args, layer_idx, group, rope, _ = pend
+            if rope is not None:                 # (the closure's launch would have rotated the row itself)
+                k = ops.rope(None, k, *rope)[1]
             ops.kv_quant_append(k, v, tk16, *args, layer_idx, group)
 
     def _step_indptr(self, b, added, device):
@@ -365,7 +386,21 @@ class MultiLayerPagedKVCache4Bit:
                 self.generation += 1
         return self._unit_buf[:rows]
 
-    def _extend_closure(self, added, args, layer_idx, had, tk_inv_t, copies):
+    def _rope_tables(self, cache_kwargs, b, added, hd):
+        """``cache_kwargs["cos"]`` / ``["sin"]`` as contiguous fp16 [bsz, added, head_dim] (themselves when they already are)."""
+        tabs = []
+        for name in ("cos", "sin"):
+            t = cache_kwargs.get(name)
+            if t is None:
+                raise ValueError(f'cache_kwargs["rotate"] needs cache_kwargs["{name}"] [bsz, added, head_dim]')
+            if t.dim() == 2:
+                t = t.unsqueeze(0)
+            if t.dim() != 3 or t.shape[1:] != (added, hd) or t.shape[0] not in (1, b):
+                raise ValueError(f'cache_kwargs["{name}"] must be [{b} or 1, {added}, {hd}], got {tuple(t.shape)}')
+            tabs.append(t.to(device=self.device, dtype=torch.float16).expand(b, added, hd).contiguous())
+        return tuple(tabs)
+
+    def _extend_closure(self, added, args, layer_idx, had, tk_inv_t, copies, rope=None):
         """The attention of a step that appended ``added`` > 1 tokens per request (a speculative verify, a follow-up prompt, a prompt fed
         in pieces): the closure takes q [bsz, added, heads, head_dim] and runs causal attention over the cache — token t of the step sees
         the rows before the step and the step's tokens 0 .. t (ops.kv_batch_extend, fq_kv_batch_extend)."""
@@ -377,6 +412,8 @@ class MultiLayerPagedKVCache4Bit:
                 raise ValueError(f"the step appended {added} tokens per request: q must be [bsz, {added}, heads, head_dim], got {tuple(q.shape)}")
             q2 = q.to(torch.float16)
             qt = None
+            if rope is not None:
+                q2 = ops.rope(q2.contiguous(), None, *rope)[0]
             if had:
                 q2 = ops.hadamard(q2.contiguous())
             elif tk_inv_t is not None:
@@ -403,22 +440,35 @@ class MultiLayerPagedKVCache4Bit:
         args = (specs["kv_data"], specs["kv_param"], specs["kv_indptr"], specs["kv_indices"], specs["last_page_offset"])
         tk16 = self._as_f16(tk)
         had = self.trans == "had"
-        orig_k, orig_v = key_states, value_states
         init = self._needs_init[layer_idx]
-        if had:                                                         # :265-266 matmul_had_cuda on the keys
-            key_states = ops.hadamard(key_states.to(torch.float16).contiguous())
         ragged_init = init and mask is not None
         # the reference's replicated layout: group_size identical copies per KV head, one of them read (read_one_copy)
         copies = self.group_size if (self.read_one_copy and 1 < self.group_size <= 8 and n_q_is_cache_heads(specs["kv_data"], heads, self.group_size)) else 1
         wgs = b * specs["kv_data"].shape[3]                 # workgroups of the decode launch: one per (request, cache head) ...
+        four_head_wgs = 0                                   # ... how many (request, four query heads) pairs the four-head launch serves (0: not that launch)
         if copies in (2, 4, 8) and hd == 128 and wgs // copies >= 32:     # (KV_MERGE_MIN_PAIRS of fq_kvcache.hip)
             wgs //= min(copies, 4)                          # ... or per (request, KV head) where one workgroup serves the group — up to four heads (fq_kv_decode_wg_heads)
-        fused = (self.fuse_append and not init and added == 1 and not self.disable_quant and key_states.dtype == torch.float16
-                 and wgs <= FUSE_APPEND_MAX_PAIRS
-                 and value_states.dtype == torch.float16 and ops.kv_decode_append_supported(specs["kv_data"], heads))
+            four_head_wgs = wgs if copies >= 4 else 0
+        elif self._shared_group in (4, 8) and hd == 128 and wgs >= 32:
+            four_head_wgs = wgs * (self._shared_group // 4)
+        fuse_geometry = (self.fuse_append and not init and added == 1 and not self.disable_quant and wgs <= FUSE_APPEND_MAX_PAIRS
+                         and value_states.dtype == torch.float16 and ops.kv_decode_append_supported(specs["kv_data"], heads))
+        # rotate: the step's rotary embedding inside the fused launch where that route is taken as it stands; everywhere else here, before
+        # the Hadamard rotation and whatever else follows (ops.rope), and on the queries in the closure
+        rope = self._rope_tables(cache_kwargs, b, added, hd) if cache_kwargs.get("rotate") else None
+        rope_fused = rope is not None and fuse_geometry and not had and mask is None and key_states.dtype == torch.float16
+        # ... or by ONE ops.rope launch for q and k in front of the fused launch, from the closure (ROPE_FUSE_MAX_FOUR_HEAD_WGS)
+        rope_in_launch = rope_fused and four_head_wgs <= ROPE_FUSE_MAX_FOUR_HEAD_WGS
+        if rope is not None and not rope_fused:
+            key_states = ops.rope(None, key_states.to(torch.float16).contiguous(), *rope)[1]
+        orig_k, orig_v = key_states, value_states
+        if had:                                                         # :265-266 matmul_had_cuda on the keys
+            key_states = ops.hadamard(key_states.to(torch.float16).contiguous())
+        fused = fuse_geometry and key_states.dtype == torch.float16
         if fused:
             # the closure's launch quantises and appends these rows itself (ops.kv_decode_append)
-            self._pending = (key_states.contiguous(), value_states.contiguous(), tk16, args, layer_idx, self.group_size)
+            self._pending = (key_states.contiguous(), value_states.contiguous(), tk16, args, layer_idx, self.group_size,
+                             (rope[0].view(b, hd), rope[1].view(b, hd)) if rope_fused else None, rope_in_launch)
             keys_t = None
         elif not self.disable_quant and not ragged_init:
             # K transform + K / V quantisation + append: one launch (fq_kv_quant_append_i4); every request appends `added`
@@ -456,7 +506,7 @@ class MultiLayerPagedKVCache4Bit:
                 keys_t = key_states if tk16 is None else torch.matmul(key_states.to(torch.float16), tk16)
             return keys_t, value_states                                 # :280-281,341-344: the un-quantised states for prefill
         if added > 1:
-            return self._extend_closure(added, args, layer_idx, had, tk_inv_t, copies)
+            return self._extend_closure(added, args, layer_idx, had, tk_inv_t, copies, rope)
         length_now = self.length                                          # (an upper bound of every request's rows: the split decode's hint)
 
         def attend(q, transposed=False):
@@ -466,15 +516,22 @@ class MultiLayerPagedKVCache4Bit:
             assert q_len == 1
             q2 = q.reshape(bq, n_q, d).to(torch.float16)
             qt = None
+            pend = self._pending
+            mine = pend is not None and pend[3] is args and pend[4] == layer_idx      # this step's rows: appended by the decode launch itself
+            if rope is not None and not (mine and pend[6] is not None):              # (rotate: ... which also rotates, or the launch of its own)
+                q2 = ops.rope(q2.contiguous(), None, rope[0].view(b, hd), rope[1].view(b, hd))[0]
             if had:                                                         # :134-138: the query side of the rotation
                 q2 = ops.hadamard(q2.contiguous())
             elif tk_inv_t is not None:                                      # :139-140: ... of the learned K transform, in the launch
                 qt = self._as_f16(tk_inv_t)
-            pend = self._pending
-            if pend is not None and pend[3] is args and pend[4] == layer_idx:      # this step's rows: appended by the decode launch itself
+            if mine:
                 self._pending = None
-                return ops.kv_decode_append(q2.contiguous(), pend[0].view(b, heads, hd), pend[1].view(b, heads, hd), pend[2], *args, layer_idx,
-                                            qt, transposed, seq_hint=length_now, read_one_copy=copies > 1).unsqueeze(1)
+                k_new, tabs = pend[0].view(b, heads, hd), pend[6]
+                if tabs is not None and not pend[7]:                        # q and k rotated by one launch in front
+                    q2, k_new = ops.rope(q2.contiguous(), k_new, *tabs)
+                    tabs = None
+                return ops.kv_decode_append(q2.contiguous(), k_new, pend[1].view(b, heads, hd), pend[2], *args, layer_idx,
+                                            qt, transposed, seq_hint=length_now, read_one_copy=copies > 1, rope=tabs).unsqueeze(1)
             self._flush_pending()
             return ops.kv_batch_decode(q2.contiguous(), *args, layer_idx, qt, transposed, seq_hint=length_now, kv_copies=copies).unsqueeze(1)
         return attend

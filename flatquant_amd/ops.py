@@ -1936,13 +1936,16 @@ def kv_transform_image(trans: torch.Tensor) -> torch.Tensor:
 def kv_decode_append(q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, trans: Optional[torch.Tensor], kv_data: torch.Tensor,
                      kv_param: torch.Tensor, kv_indptr: torch.Tensor, kv_indices: torch.Tensor, last_page_offset: torch.Tensor,
                      layer_idx: int, q_trans: Optional[torch.Tensor] = None, transpose_out: bool = False, seq_hint: int = 0,
-                     split: bool = True, read_one_copy: bool = False) -> torch.Tensor:
+                     split: bool = True, read_one_copy: bool = False, rope=None) -> torch.Tensor:
     """kv_quant_append(k_new, v_new, trans, ...) + kv_batch_decode(q, ...) of a decode step as ONE launch (fq_kv_decode_append_i4, round 6): the
     index tensors already count the new token (as for kv_quant_append), k_new / v_new [batch, kv_heads, head_dim] fp16 are its keys / values
     (the cache's heads are a multiple of kv_heads: the reference's replicated layout, or the shared one), q [batch, heads, head_dim]. The
     cache contents and the attention output are bit-identical to the two calls. INT4 cache, head_dim 128, page_size % 16 == 0
     (``kv_decode_append_supported``). ``read_one_copy``: on the replicated layout (cache heads = query heads = kv_heads x copies) the launch
-    reads the first copy of every group (as kv_batch_decode(kv_copies=...)) and writes the new row to all of them."""
+    reads the first copy of every group (as kv_batch_decode(kv_copies=...)) and writes the new row to all of them.
+    ``rope`` = (cos, sin), each [batch, head_dim] fp16 (round 8, fq_kv_decode_append_rope_i4): q and k_new are the UN-rotated projections and the
+    launch applies the step's rotary embedding to them itself — the queries before ``q_trans``, the new K row before ``trans``, never V: cache
+    contents and output bit-identical to ``rope(q, k_new, cos, sin)`` followed by this call without the argument."""
     _chk(q, "q"), _chk(k_new, "k_new"), _chk(v_new, "v_new"), _chk(kv_data, "kv_data", torch.uint8), _chk(kv_param, "kv_param")
     n_layers, cache_heads, page_size, hd = _kv_geometry(kv_data)
     batch = _chk_kv_index(kv_indptr, kv_indices, last_page_offset)
@@ -1956,6 +1959,12 @@ def kv_decode_append(q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, 
         _chk(q_trans, "q_trans")
         if q_trans.shape != (hd, hd):
             raise ValueError("q_trans must be [head_dim, head_dim]")
+    cos = sin = None
+    if rope is not None:
+        cos, sin = rope
+        _chk(cos, "cos"), _chk(sin, "sin")
+        if cos.numel() != batch * hd or sin.numel() != batch * hd or cos.shape[-1] != hd or sin.shape[-1] != hd:
+            raise ValueError(f"rope = (cos, sin) must each be [{batch}, {hd}] (the step's row of the tables per request)")
     img = kv_transform_image(trans) if trans is not None else None
     o = torch.empty((batch, hd, heads) if transpose_out else (batch, heads, hd), dtype=torch.float16, device=q.device)
     if batch == 0:
@@ -1966,11 +1975,52 @@ def kv_decode_append(q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, 
         nbytes = int(lib.fq_kv_decode_workspace_bytes_gqa(batch, heads // share, share, hd)) if split else 0
         stream = _stream(q)
         ws = _kv_split_workspace((q.device.index, stream.value, batch * heads, hd), nbytes, q.device) if nbytes > 0 else None
-        check(lib.fq_kv_decode_append_i4(_ptr(o), _ptr(q), _ptr(q_trans), 1 if transpose_out else 0, _ptr(k_new), _ptr(v_new), _ptr(img), src_heads,
-                                         _ptr(kv_data), _ptr(kv_param), _ptr(kv_indptr), _ptr(kv_indices), _ptr(last_page_offset),
-                                         n_layers, layer_idx, cache_heads, q_group, page_size, hd, batch, int(seq_hint), 1 if one else 0, _ptr(ws),
-                                         nbytes if ws is not None else 0, stream))
+        args = (_ptr(o), _ptr(q), _ptr(q_trans), 1 if transpose_out else 0, _ptr(k_new), _ptr(v_new), _ptr(img), src_heads,
+                _ptr(kv_data), _ptr(kv_param), _ptr(kv_indptr), _ptr(kv_indices), _ptr(last_page_offset),
+                n_layers, layer_idx, cache_heads, q_group, page_size, hd, batch, int(seq_hint), 1 if one else 0, _ptr(ws),
+                nbytes if ws is not None else 0, stream)
+        if cos is None:
+            check(lib.fq_kv_decode_append_i4(*args))
+        else:
+            check(lib.fq_kv_decode_append_rope_i4(*args, _ptr(cos), _ptr(sin)))
     return o
+
+
+def rope(q: Optional[torch.Tensor], k: Optional[torch.Tensor], cos: torch.Tensor, sin: torch.Tensor, out=None):
+    """Rotary position embedding of queries and keys in ONE launch (fq_rope_f16, round 8): transformers' ``apply_rotary_pos_emb(q, k, cos, sin,
+    unsqueeze_dim=2)`` on fp16 tensors, bit for bit — ``(x * cos) + (rotate_half(x) * sin)`` with its three fp16 roundings. q [..., q_heads,
+    head_dim] and k [..., k_heads, head_dim] over the same leading (token) dimensions, cos / sin [..., head_dim] with one row per token, taken
+    as given. Either of q, k may be None. ``out`` = (q_out, k_out): where the results go — each may be its own input (in place); default: new
+    tensors. -> (q_out, k_out), None for a tensor that was not given. head_dim 64 or 128."""
+    if q is None and k is None:
+        raise ValueError("rope: q and k are both None")
+    _chk(cos, "cos"), _chk(sin, "sin")
+    hd = cos.shape[-1]
+    tokens = cos.numel() // hd if hd else 0
+    if cos.shape != sin.shape:
+        raise ValueError("rope: cos and sin must have the same shape [..., head_dim]")
+    q_out, k_out = out if out is not None else (None, None)
+    heads = []
+    outs = []
+    for t, o, name in ((q, q_out, "q"), (k, k_out, "k")):
+        if t is None:
+            heads.append(0), outs.append(None)
+            continue
+        _chk(t, name)
+        if t.dim() < 2 or t.shape[-1] != hd or t.numel() != tokens * t.shape[-2] * hd:
+            raise ValueError(f"rope: {name} must be [..., heads, {hd}] with {tokens} tokens (cos / sin hold one row per token), got {tuple(t.shape)}")
+        if o is None:
+            o = torch.empty_like(t)
+        else:
+            _chk(o, name + "_out")
+            if o.shape != t.shape:
+                raise ValueError(f"rope: {name}_out must have the shape of {name}")
+        heads.append(t.shape[-2]), outs.append(o)
+    if tokens == 0:
+        return outs[0], outs[1]
+    with _on(cos.device):
+        check(lib.fq_rope_f16(_ptr(outs[0]), _ptr(outs[1]), _ptr(q), _ptr(k), _ptr(cos), _ptr(sin), tokens, heads[0], heads[1], hd, hd, _stream(cos)))
+    return outs[0], outs[1]
 
 
 def kv_decode_append_supported(kv_data: torch.Tensor, src_heads: int) -> bool:

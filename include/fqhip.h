@@ -598,7 +598,7 @@ int fq_kv_dequant_f16(const void* q, const void* param, int64_t rows, int head_d
  *   kv_cache.py:286-296, which repeats the tensors first): k, v and their params hold num_heads / g heads and cache head h
  *   receives head h / g — the repeat_interleave happens in the scatter.
  * fq_kv_batch_decode_i4: one query token per request, q and o [batch, num_heads, head_dim] fp16 (decode.cuh:492-683,
- *   no rotary embedding, softmax scale 1/sqrt(head_dim)): o = softmax(q . K^T / sqrt(hd)) . V over the request's cached
+ *   no rotary embedding inside — fq_rope_f16 / fq_kv_decode_append_rope_i4 below —, softmax scale 1/sqrt(head_dim)): o = softmax(q . K^T / sqrt(hd)) . V over the request's cached
  *   rows, K and V de-quantised as n * scale - zero (quantization.cuh:58-80), fp32 arithmetic. head_dim in {64, 128}.
  */
 int fq_kv_append_i4(void* kv_data, void* kv_param, const void* kv_indptr, const void* kv_indices,
@@ -659,6 +659,25 @@ int fq_kv_decode_append_i4(void* o, const void* q, const void* q_trans, int tran
                            const void* k_trans_image, int src_heads, const void* kv_data, const void* kv_param, const void* kv_indptr,
                            const void* kv_indices, const void* last_page_offset, int num_layers, int layer_idx, int num_kv_heads, int q_group,
                            int page_size, int head_dim, int batch_size, int seq_hint, int read_one_copy, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ROTARY POSITION EMBEDDING (round 8) — what transformers' apply_rotary_pos_emb(q, k, cos, sin, unsqueeze_dim=2) computes on fp16 tensors, between
+ * the q / k / v projections and the cache update (modeling_llama.py:105): about ten element-wise torch launches per layer and step.
+ *   out[j] = rn16(rn16(x[j] cos[j]) + rn16(r[j] sin[j])),  r[j] = -x[j + head_dim / 2] for j < head_dim / 2, x[j - head_dim / 2] otherwise:
+ * THREE fp16 roundings, bit-identical to the torch expression (a fused multiply-add differs in about three elements of ten). cos / sin
+ * [tokens, head_dim] fp16 are taken as given: their halves need not be equal, frequency scaling and attention_scaling stay the caller's.
+ * fq_rope_f16: q [tokens, q_heads, head_dim] and k [tokens, k_heads, head_dim] in ONE launch; q or k may be NULL (its heads and output are then
+ *   ignored), not both; q_out / k_out may be q / k themselves (in place). head_dim 64 or 128 and rotary_dim == head_dim (partial rotary:
+ *   FQ_EUNSUPPORTED); 16-byte aligned tensors.
+ * fq_kv_decode_append_rope_i4: fq_kv_decode_append_i4 with the step's tables cos / sin [batch, head_dim] (both, or both NULL = that function): the
+ *   launch rotates its queries (before q_trans, modeling_llama.py:105,129) and the new K row (before the K transform) itself; V is never
+ *   rotated. q and k_new are the UN-rotated projections. Cache contents and o are bit-identical to fq_rope_f16 followed by fq_kv_decode_append_i4. */
+int fq_rope_f16(void* q_out, void* k_out, const void* q, const void* k, const void* cos, const void* sin, int64_t tokens, int q_heads, int k_heads,
+                int head_dim, int rotary_dim, void* stream);
+int fq_kv_decode_append_rope_i4(void* o, const void* q, const void* q_trans, int transpose_out, const void* k_new, const void* v_new,
+                                const void* k_trans_image, int src_heads, const void* kv_data, const void* kv_param, const void* kv_indptr,
+                                const void* kv_indices, const void* last_page_offset, int num_layers, int layer_idx, int num_kv_heads, int q_group,
+                                int page_size, int head_dim, int batch_size, int seq_hint, int read_one_copy, void* workspace, int64_t workspace_bytes,
+                                void* stream, const void* cos, const void* sin);
 
 /* The reference's replicated layout READ ONE COPY PER GROUP (round 6, third session). kv_cache.py:286-296 stores every KV head once per query head
  * of its group: `copies` consecutive cache heads with identical rows (fq_kv_quant_append_i4 / fq_kv_append_* with group_size = copies write them

@@ -3,8 +3,9 @@
 from a captured HIP graph (from Python every launch costs ~10 us of allocation + ctypes, more than most of these kernels):
 norm + q/k/v transform (one launch) -> three Linear4bit (weight-streaming kernel) -> K transform + K/V INT4 pack ->
 paged-cache append -> INT4 decode attention -> o_proj head transform -> Linear4bit -> norm + up/gate transform ->
-two Linear4bit -> SiLU.mul + down_proj transform -> Linear4bit.  RoPE and the residual adds are left out (torch ops of
-the host model). Llama-3-8B shapes, random weights."""
+two Linear4bit -> SiLU.mul + down_proj transform -> Linear4bit.  The residual adds are left out (torch ops of the host
+model); the rotary position embedding between the projections and the cache is chosen with --rope. Llama-3-8B shapes,
+random weights."""
 import argparse
 import os
 import sys
@@ -32,6 +33,10 @@ def main():
     ap.add_argument("--single", action="store_true", help="one launch per projection (rounds 1-4) instead of the multi-problem launches")
     ap.add_argument("--fp16", action="store_true", help="also time the same step in fp16 (nn.Linear, rms_norm, SiLU.mul, the fp16 configuration of the paged cache) "
                                                         "— the baseline of the reference's decode table, README.md:300-310")
+    ap.add_argument("--rope", choices=["none", "torch", "launch", "fused"], default="none",
+                    help="rotary position embedding of q and k between the projections and the cache (modeling_llama.py:105): none (rounds 1-7: left out), "
+                         "torch (transformers' apply_rotary_pos_emb: ~ten element-wise launches), launch (ops.rope: one launch for q and k), fused "
+                         "(cache_kwargs['rotate']: inside the append + attention launch). The fp16 baseline step gets the torch ops unless 'none'")
     a = ap.parse_args()
     hidden, ffn, heads, kv_heads, hd = 4096, 14336, 32, 8, 128
     dev = torch.device("cuda")
@@ -76,6 +81,28 @@ def main():
         cache.update(torch.randn(a.bsz, a.cache, kv_heads, hd, generator=g, device=dev).half(),
                      torch.randn(a.bsz, a.cache, kv_heads, hd, generator=g, device=dev).half(), li, dict(kw))
     x = torch.randn(a.bsz, 1, hidden, generator=g, device=dev).half()
+    # the step's rotary tables [bsz, 1, hd] (every request at its own position), as the host model hands them to the layer
+    pos = (a.cache + torch.arange(a.bsz, device=dev, dtype=torch.float32) * 3.0)[:, None]
+    freqs = pos * (1.0 / (5e5 ** (torch.arange(0, hd, 2, device=dev, dtype=torch.float32) / hd)))[None, :]
+    cos = torch.cat((freqs, freqs), dim=-1).cos().half()[:, None, :].contiguous()
+    sin = torch.cat((freqs, freqs), dim=-1).sin().half()[:, None, :].contiguous()
+    kw_step = dict(kw, cos=cos, sin=sin, rotate=True) if a.rope == "fused" else dict(kw)
+
+    def rotate_half(t):
+        return torch.cat((-t[..., hd // 2:], t[..., :hd // 2]), dim=-1)
+
+    def rope_torch(q, k):       # transformers' apply_rotary_pos_emb(q, k, cos, sin, unsqueeze_dim=2)
+        c, s_ = cos.unsqueeze(2), sin.unsqueeze(2)
+        return (q * c) + (rotate_half(q) * s_), (k * c) + (rotate_half(k) * s_)
+
+    def rope_qk(q, k, mode=None):
+        """q [bsz, 1, heads, hd], k [bsz, 1, kv_heads, hd] as the cache takes them under --rope"""
+        mode = mode or a.rope
+        if mode == "torch":
+            return rope_torch(q, k)
+        if mode == "launch":
+            return ops.rope(q, k, cos, sin)
+        return q, k              # none; fused: the cache rotates (kw_step)
 
     def layer_step(h, li):
         qkv_t, ug_t, o_t, down_t, q_l, k_l, v_l, o_l, up_l, gate_l, down_l = layers[li]
@@ -84,8 +111,9 @@ def main():
             q, k, v = deploy.nn.linear.linear4bit_multi([q_l, k_l, v_l], [pq, pk, pv]) if not a.single else (q_l(pq), k_l(pk), v_l(pv))
         else:   # (round 6) the transform as the projections' prologue where that pays (<= 8 tokens), the two launches otherwise
             q, k, v = deploy.nn.fused_transform_linear(h, qkv_t, [q_l, k_l, v_l], norm=norm)
-        attend = cache.update(k.view(a.bsz, 1, kv_heads, hd), v.view(a.bsz, 1, kv_heads, hd), li, dict(kw))
-        att_t = attend(q.view(a.bsz, 1, heads, hd), transposed=True)                # [bsz, 1, hd, heads]
+        q4, k4 = rope_qk(q.view(a.bsz, 1, heads, hd), k.view(a.bsz, 1, kv_heads, hd))
+        attend = cache.update(k4, v.view(a.bsz, 1, kv_heads, hd), li, dict(kw_step))
+        att_t = attend(q4, transposed=True)                # [bsz, 1, hd, heads]
         po = o_t(att_t)
         po.quantized_x = po.quantized_x.contiguous().reshape(a.bsz, 1, -1)
         h2 = o_l(po)
@@ -116,8 +144,9 @@ def main():
             for li in range(L):
                 qkv_t, ug_t, o_t, down_t, q_l, k_l, v_l, o_l, up_l, gate_l, down_l = layers[li]
                 q, k, v = deploy.nn.fused_transform_linear(h, qkv_t, [q_l, k_l, v_l], norm=norm)
-                attend = cache.update(k.view(a.bsz, 1, kv_heads, hd), v.view(a.bsz, 1, kv_heads, hd), li, dict(kw))
-                po = o_t(attend(q.view(a.bsz, 1, heads, hd), transposed=True))
+                q4, k4 = rope_qk(q.view(a.bsz, 1, heads, hd), k.view(a.bsz, 1, kv_heads, hd))
+                attend = cache.update(k4, v.view(a.bsz, 1, kv_heads, hd), li, dict(kw_step))
+                po = o_t(attend(q4, transposed=True))
                 po.quantized_x = po.quantized_x.contiguous().reshape(a.bsz, 1, -1)
                 yu, yg = deploy.nn.fused_transform_linear(o_l(po), ug_t, [up_l, gate_l], norm=norm)
                 h = down_l(down_t(yg, up=yu))
@@ -197,7 +226,8 @@ def main():
                 fq, fk, fv, fo, fu, fg, fd = f16[li]
                 xn = F.rms_norm(h, (hidden,), w1, 1e-6)
                 q, k, v = fq(xn), fk(xn), fv(xn)
-                att = cache16.update(k.view(a.bsz, 1, kv_heads, hd), v.view(a.bsz, 1, kv_heads, hd), li, {})(q.view(a.bsz, 1, heads, hd))
+                q4, k4 = rope_qk(q.view(a.bsz, 1, heads, hd), k.view(a.bsz, 1, kv_heads, hd), "none" if a.rope == "none" else "torch")
+                att = cache16.update(k4, v.view(a.bsz, 1, kv_heads, hd), li, {})(q4)
                 h2 = fo(att.reshape(a.bsz, 1, hidden))
                 xn2 = F.rms_norm(h2, (hidden,), w1, 1e-6)
                 h = fd(F.silu(fg(xn2)) * fu(xn2))
@@ -255,7 +285,7 @@ def main():
           f"({gd.captures} capture(s), {gd.replays} replays, {gd.eager_calls} eager warm-up calls); output finite: {bool(torch.isfinite(y2.float()).all())}"
           + (f"   | fp16 step through the same helper: {trans16:.1f} us (captures / replays / eager {g16_counts}) -> {trans16 / transparent:.2f}x; against the EAGER fp16 step "
              f"({eager16:.1f} us): {eager16 / transparent:.2f}x" if a.fp16 else ""))
-    print(f"Llama-3-8B decoder layer, decode step, {a.bsz} requests x {a.cache} cached tokens"
+    print(f"Llama-3-8B decoder layer, decode step [rope: {a.rope}], {a.bsz} requests x {a.cache} cached tokens"
           + (f" [{L} layers with their own weights per step: {L * 109} MB of INT4 weights streamed per replay]" if L > 1 else "") + f": {us:.1f} us per layer from a "
           f"captured graph ({eager:.1f} us launched eagerly from Python); output finite: {bool(torch.isfinite(y.float()).all())}"
           + (f"   | the same step in fp16 (fp16 paged cache): {us16:.1f} us captured ({eager16:.1f} eager): speed-up {us16 / us:.2f}x captured, "
