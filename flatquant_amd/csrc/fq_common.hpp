@@ -260,6 +260,18 @@ __device__ __forceinline__ float fq_group4_reduce(float v, Op op) {
     return v;
 }
 
+// FQ_QUANT_F16 with a token so small that its fp16 scale underflows (m / 7 below half the smallest fp16 subnormal: a token of a few
+// subnormals): the reference stores the scale 0 and divides by it — 0 / 0 is a NaN that quant.cu:40's __half2int_rn turns into digit 0,
+// y / 0 = +-Inf saturates, every fake-quant value is 0 x q = 0. fq_token_scale then returns this value instead of 0 for the quantiser to
+// divide by (with 0 the fp32 quantisers computed 0 / 0 -> -8: fmaxf drops the NaN), and callers store and dequantise with (T)scale.
+//   T = f16: (f16)2^-100 == 0, the stored scale. A zero element keeps digit 0. Every non-zero element saturates as in the reference: an fp16
+//     y is at least 2^-24, and an fp32 y (no FQ_ROUND_Y_F16) is an fp32 sum of products of fp16 values, each a multiple of 2^-48, so it is
+//     0 or at least 2^-48 — times 2^100 beyond 8 either way. y / 2^-100 stays finite in fp32 (m < 7 x 2^-25), so no Inf x 0 arises in the
+//     reciprocal forms. The quantisers that divide in T by (T)scale == 0 (fq_quant1_h) make the NaN of 0 / 0 digit 0 themselves.
+//   T = bf16: NOT covered. A bf16 scale underflows only for m <= 3 x 2^-133 (bf16 has fp32's exponent range); no fp32 normal rounds to a
+//     bf16 zero, so such a token stores 2^-100 and gets all-zero digits where the reference saturates. No model activation comes near.
+constexpr float FQ_SCALE_UNDERFLOW = 0x1p-100f;
+
 // scale from (xmax, xmin) of one token and one clip set; see header comment for the pinned arithmetic.
 template <int FLAGS, typename T = f16>
 __device__ __forceinline__ float fq_token_scale(float xmax, float xmin, float sig_max, float sig_min,
@@ -272,7 +284,7 @@ __device__ __forceinline__ float fq_token_scale(float xmax, float xmin, float si
         // deploy Quantizer(input_clip_ratio) (deploy/nn/quantization.py:30): (max|x| / 7).to(fp16) * ratio, both steps in T
         const float m0 = fmaxf(fabsf(xmin), xmax);
         if (m0 == 0.0f) return 1.0f;   // (quantise with 1: every digit is 0; the caller stores the reference's scale, 0)
-        return (float)fq_mul_to<T>((float)(T)(m0 / 7.0f), sig_max);
+        return (float)fq_mul_to<T>((float)(T)(m0 / 7.0f), sig_max);   // (can underflow to 0 as well: not handled, see FQ_SCALE_UNDERFLOW)
     }
     if ((FLAGS & FQ_QUANT_F16) && (rt_flags & FQ_SIG_F16)) {
         // deploy.nn.Quantizer(lac=True), deploy/nn/quantization.py:21-22: an fp16 [rows, 1] tensor times a 0-dim fp32
@@ -295,6 +307,7 @@ __device__ __forceinline__ float fq_token_scale(float xmax, float xmin, float si
         // (T = bf16: the fp32 quotient of two 8-bit significands rounded to bf16 is the correctly rounded bf16 quotient)
         scale = (float)(T)(m / 7.0f);
         if (m == 0.0f) scale = 1.0f;
+        else if (scale == 0.0f) scale = FQ_SCALE_UNDERFLOW;
     } else {
         scale = m / 7.0f;
         if (m == 0.0f) scale = 1.0f;
@@ -320,7 +333,7 @@ __device__ __forceinline__ int fq_quant1_h(f16 y, f16 s) {
     const f16 t = y / s;
     float r = __builtin_rintf((float)t);
     r = __builtin_amdgcn_fmed3f(r, -8.0f, 7.0f);
-    return (int)r;
+    return t != t ? 0 : (int)r;   // 0 / 0 under an underflowed scale (FQ_SCALE_UNDERFLOW): __half2int_rn(NaN) == 0
 }
 // bf16: torch evaluates x / scale in fp32 opmath and rounds the quotient to bf16 (a quotient of two 8-bit significands is
 // never within 2^-24 of a bf16 rounding boundary unless it lies on it: the double rounding is harmless)
@@ -328,7 +341,7 @@ __device__ __forceinline__ int fq_quant1_h(bf16 y, bf16 s) {
     const float t = (float)(bf16)((float)y / (float)s);
     float r = __builtin_rintf(t);
     r = __builtin_amdgcn_fmed3f(r, -8.0f, 7.0f);
-    return (int)r;
+    return t != t ? 0 : (int)r;
 }
 
 // x_up * act_fn(x_gate) in front of a down_proj transform (deploy/transformers/modeling_llama.py:277-278, fp16 tensors):
