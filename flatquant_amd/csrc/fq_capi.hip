@@ -79,6 +79,8 @@ int fq_launch_kv_extend(f16* o, const f16* q, const f16* qt, int transpose_out, 
                         const int* indices, const int* last, int num_layers, int layer_idx, int num_cache_heads, int q_group, int copies,
                         int q_len, int page_size, int head_dim, int batch, int seq_hint, float* ws, int64_t ws_bytes, hipStream_t stream,
                         bool f16_cache);
+int fq_launch_prefill_attn(f16* o, const f16* q, const f16* qt, const f16* k, const f16* v, const int* seq_start, const int* seq_len, int batch,
+                           int seq, int q_heads, int kv_heads, hipStream_t stream);   // fq_prefill_attn.hip
 int fq_launch_silu_mul(const f16* gate, const f16* up, f16* y, int64_t n, int n_cu, hipStream_t stream);
 int fq_launch_silu_hadamard_quant(const f16* gate, const f16* up, int64_t rows, int n, int K, const f16* hadK, float scale,
                                   float sig_max, float sig_min, uint8_t* q, f16* scale_out, int n_cu, hipStream_t stream);
@@ -1390,6 +1392,21 @@ int fq_kv_batch_extend(int fp16_cache, void* o, const void* q, const void* q_tra
                              q_len, page_size, head_dim, batch_size, seq_hint, (float*)workspace, workspace_bytes, (hipStream_t)stream,
                              fp16_cache != 0);
     return check_launch(rc, what);
+}
+
+int fq_prefill_attention_f16(void* o, const void* q, const void* q_trans, const void* k, const void* v, const void* seq_start,
+                             const void* seq_len, int batch_size, int seq, int q_heads, int kv_heads, int head_dim, void* stream) {
+    const char* what = "fq_prefill_attention_f16";
+    FQ_NEED_ALIGN16(what, o, q, q_trans, k, v, seq_start, seq_len);
+    if (head_dim == 64) return fail(FQ_EUNSUPPORTED, "%s: head_dim=64 (128 only)", what);
+    if (head_dim != 128) return fail(FQ_EINVAL, "%s: head_dim=%d (128 only)", what, head_dim);
+    if (batch_size < 1 || seq < 1 || q_heads < 1 || kv_heads < 1 || q_heads % kv_heads)
+        return fail(FQ_EINVAL, "%s: batch_size=%d, seq=%d, q_heads=%d, kv_heads=%d: all >= 1, q_heads a multiple of kv_heads", what, batch_size, seq,
+                    q_heads, kv_heads);
+    if ((seq_start == nullptr) != (seq_len == nullptr)) return fail(FQ_EINVAL, "%s: seq_start and seq_len go together (both or neither)", what);
+    if (!o || !q || !k || !v) return fail(FQ_EINVAL, "%s: NULL pointer", what);
+    return check_launch(fq_launch_prefill_attn((f16*)o, (const f16*)q, (const f16*)q_trans, (const f16*)k, (const f16*)v, (const int*)seq_start,
+                                               (const int*)seq_len, batch_size, seq, q_heads, kv_heads, (hipStream_t)stream), what);
 }
 
 static int rowquant_impl(const char* what, int dt, const void* x, int64_t rows, int cols, const float* sig_max, const float* sig_min,

@@ -1882,6 +1882,52 @@ def kv_batch_extend(q: torch.Tensor, kv_data: torch.Tensor, kv_param: torch.Tens
     return o
 
 
+def prefill_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_trans: Optional[torch.Tensor] = None,
+                      seq_start: Optional[torch.Tensor] = None, seq_len: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Causal self-attention of a prompt (fq_prefill_attention_f16): q [batch, seq, q_heads, 128], k / v [batch, seq, kv_heads, 128] fp16 -> o
+    like q. Query head h reads KV head h // (q_heads // kv_heads); scores / sqrt(head_dim), fp32 softmax, o rounded to fp16 once.
+    ``q_trans`` [128, 128]: the query is fp16(q . q_trans) inside the launch. ``seq_start`` / ``seq_len`` (int32 [batch], both or neither):
+    request b's tokens are positions seq_start[b] .. seq_start[b] + seq_len[b] - 1, causal within them; o outside the range is zeros and
+    q / k / v outside it never change a result. Non-contiguous inputs are copied. head_dim 128."""
+    q, k, v = (t.contiguous() if isinstance(t, torch.Tensor) else t for t in (q, k, v))
+    _chk(q, "q"), _chk(k, "k"), _chk(v, "v")
+    if k.device != q.device or v.device != q.device:
+        raise ValueError(f"q, k, v must be on one device, got {q.device}, {k.device}, {v.device}")
+    if q.dim() != 4 or k.dim() != 4 or k.shape != v.shape or q.shape[:2] != k.shape[:2] or q.shape[3] != k.shape[3]:
+        raise ValueError(f"q [batch, seq, q_heads, head_dim] and k / v [batch, seq, kv_heads, head_dim] expected, got {tuple(q.shape)}, "
+                         f"{tuple(k.shape)}, {tuple(v.shape)}")
+    batch, seq, heads, hd = q.shape
+    kv_heads = k.shape[2]
+    if kv_heads < 1 or heads < 1 or heads % kv_heads:
+        raise ValueError(f"q_heads={heads} must be a multiple of kv_heads={kv_heads} (both >= 1)")
+    if q_trans is not None:
+        q_trans = q_trans.contiguous() if isinstance(q_trans, torch.Tensor) else q_trans
+        _chk(q_trans, "q_trans")
+        if q_trans.shape != (hd, hd) or q_trans.device != q.device:
+            raise ValueError("q_trans must be [head_dim, head_dim] on q's device")
+    if (seq_start is None) != (seq_len is None):
+        raise ValueError("seq_start and seq_len go together (both or neither)")
+    if seq_start is not None:
+        seq_start, seq_len = seq_start.contiguous(), seq_len.contiguous()
+        for t, n in ((seq_start, "seq_start"), (seq_len, "seq_len")):
+            _chk(t, n, torch.int32)
+            if t.shape != (batch,):
+                raise ValueError(f"{n} must be [batch] = [{batch}], got {tuple(t.shape)}")
+            if t.device != q.device:
+                raise ValueError(f"{n} is on {t.device}, q on {q.device}: the launch reads it on q's device")
+        if seq_start.data_ptr() % 16:
+            seq_start = seq_start.clone()
+        if seq_len.data_ptr() % 16:
+            seq_len = seq_len.clone()
+    o = torch.empty((batch, seq, heads, hd), dtype=torch.float16, device=q.device)
+    if batch == 0 or seq == 0:
+        return o
+    with _on(q.device):
+        check(lib.fq_prefill_attention_f16(_ptr(o), _ptr(q), _ptr(q_trans), _ptr(k), _ptr(v), _ptr(seq_start), _ptr(seq_len), batch, seq,
+                                           heads, kv_heads, hd, _stream(q)))
+    return o
+
+
 # Fragment images of the K transform for kv_decode_append (fq_kv_transform_image_f16: 32 KB per layer at head_dim 128), by (device, transform):
 # [image, transform, event of the preparing launch, {"done", "streams"}]. Same protocol as the Kronecker images: the entry keeps the transform alive,
 # in-place updates miss (ver), another stream waits for the preparing launch once; under capture only an image known complete (images_ready())

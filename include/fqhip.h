@@ -713,6 +713,25 @@ int fq_kv_batch_extend(int fp16_cache, void* o, const void* q, const void* q_tra
                        int layer_idx, int num_cache_heads, int q_group, int copies, int q_len, int page_size, int head_dim, int batch_size,
                        int seq_hint, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* THE PROMPT'S OWN ATTENTION: causal flash-style self-attention over the un-quantised (transformed) states the cache returns on its first call
+ * per layer — what the reference hands to flash-attn (deploy/transformers/modeling_llama.py:125-137: transformers' _flash_attention_forward(
+ * query_states @ trans_matrix_k_inv_t, key_states, value_states, query_length, attention_mask, is_causal=True)).
+ *   q, o: [batch_size, seq, q_heads, head_dim] fp16; k, v: [batch_size, seq, kv_heads, head_dim] fp16, all contiguous; query head h reads KV
+ *      head h / (q_heads / kv_heads) (repeat_kv's order, as the decode launches). Scores q . k / sqrt(head_dim), softmax and sums in fp32, o
+ *      rounded to fp16 once. q_trans [head_dim, head_dim] fp16 or NULL: the query is q' = fp16(q . q_trans) inside the launch (the q_trans
+ *      of fq_kv_batch_decode_* / fq_kv_batch_extend).
+ *   seq_start, seq_len: int32 [batch_size], both or neither (NULL: every request is positions 0 .. seq - 1). Request b's tokens are positions
+ *      seq_start[b] .. seq_start[b] + seq_len[b] - 1 and position seq_start[b] + t attends seq_start[b] .. seq_start[b] + t. o outside the
+ *      range is written as ZEROS (pad_input's behaviour); q / k / v outside it are never read in a way that changes a result (NaN there is
+ *      harmless); seq_len[b] = 0 gives an all-zero request. A range is clipped to the tensor.
+ *      Values INSIDE a range are assumed finite: a masked key's V row still meets its zero weight on the matrix pipe (0 . NaN = NaN).
+ *   Any seq >= 1 (tails are masked in the launch). One launch, no workspace, no atomics: two runs are bit-identical, and a ranged request
+ *      equals, bit for bit, the launch on its tokens alone.
+ *   Every tensor 16-byte aligned; head_dim 128 (64: FQ_EUNSUPPORTED, anything else: FQ_EINVAL); batch_size / seq / heads < 1, q_heads not a
+ *      multiple of kv_heads, or exactly one of seq_start / seq_len NULL: FQ_EINVAL. */
+int fq_prefill_attention_f16(void* o, const void* q, const void* q_trans, const void* k, const void* v, const void* seq_start,
+                             const void* seq_len, int batch_size, int seq, int q_heads, int kv_heads, int head_dim, void* stream);
+
 /*
  * The fp16 configuration of the same cache (MultiLayerPagedKVCache4Bit(disable_quant=True), kv_cache.py:177-190;
  * init_kv_f16 / append_kv_f16 / batch_decode_f16, kv_cache.py:107-137): kv_data [pages, num_layers, 2, num_heads, page_size,
