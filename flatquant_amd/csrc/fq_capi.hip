@@ -79,6 +79,9 @@ int fq_launch_kv_extend(f16* o, const f16* q, const f16* qt, int transpose_out, 
                         const int* indices, const int* last, int num_layers, int layer_idx, int num_cache_heads, int q_group, int copies,
                         int q_len, int page_size, int head_dim, int batch, int seq_hint, float* ws, int64_t ws_bytes, hipStream_t stream,
                         bool f16_cache);
+int fq_launch_kv_chunk_extend(f16* o, const f16* q, const f16* qt, int transpose_out, const void* kv_data, const void* kv_param, const int* indptr,
+                              const int* indices, const int* last, int num_layers, int layer_idx, int num_cache_heads, int q_group, int copies,
+                              int q_len, int page_size, int head_dim, int batch, hipStream_t stream, bool f16_cache);   // fq_kv_chunk_extend.hip
 int fq_launch_prefill_attn(f16* o, const f16* q, const f16* qt, const f16* k, const f16* v, const int* seq_start, const int* seq_len, int batch,
                            int seq, int q_heads, int kv_heads, hipStream_t stream);   // fq_prefill_attn.hip
 int fq_launch_silu_mul(const f16* gate, const f16* up, f16* y, int64_t n, int n_cu, hipStream_t stream);
@@ -1391,6 +1394,30 @@ int fq_kv_batch_extend(int fp16_cache, void* o, const void* q, const void* q_tra
                              (const int*)kv_indices, (const int*)last_page_offset, num_layers, layer_idx, num_cache_heads, q_group, copies,
                              q_len, page_size, head_dim, batch_size, seq_hint, (float*)workspace, workspace_bytes, (hipStream_t)stream,
                              fp16_cache != 0);
+    return check_launch(rc, what);
+}
+
+int fq_kv_chunk_extend(int fp16_cache, void* o, const void* q, const void* q_trans, int transpose_out, const void* kv_data, const void* kv_param,
+                       const void* kv_indptr, const void* kv_indices, const void* last_page_offset, int num_layers, int layer_idx,
+                       int num_cache_heads, int q_group, int copies, int q_len, int page_size, int head_dim, int batch_size, void* stream) {
+    const char* what = "fq_kv_chunk_extend";
+    if (q_len < 1) return fail(FQ_EINVAL, "%s: q_len=%d must be >= 1", what, q_len);
+    int rc = kv_geometry_ok(what, num_layers, layer_idx, num_cache_heads, page_size, head_dim, batch_size);
+    if (rc != FQ_OK) return rc;
+    if (q_group < 1 || q_group > 64 || copies < 1 || copies > 8 || q_group % copies || num_cache_heads % copies)
+        return fail(FQ_EINVAL, "%s: q_group=%d (1..64) must be a multiple of copies=%d (1..8), which must divide num_cache_heads=%d", what, q_group,
+                    copies, num_cache_heads);
+    if (head_dim != 128) return fail(FQ_EUNSUPPORTED, "%s: head_dim=%d (128 only)", what, head_dim);
+    if (q_group != 1 && q_group != 2 && q_group != 4 && q_group != 8)
+        return fail(FQ_EUNSUPPORTED, "%s: q_group=%d (1, 2, 4 or 8; fq_kv_batch_extend takes any group)", what, q_group);
+    if (!o || !q || !kv_data || (!fp16_cache && !kv_param) || !kv_indptr || !kv_indices || !last_page_offset)
+        return fail(FQ_EINVAL, "%s: NULL pointer", what);
+    FQ_NEED_ALIGN16(what, o, q, kv_data, q_trans);
+    if ((int64_t)q_len * q_group > 0x7FFFFF00 || (int64_t)batch_size * (num_cache_heads / copies) * (((int64_t)q_len * q_group + 127) / 128) > 0x7FFFFFFF)
+        return fail(FQ_EINVAL, "%s: batch_size=%d x %d row sets x q_len=%d is more than one launch takes", what, batch_size, num_cache_heads / copies, q_len);
+    rc = fq_launch_kv_chunk_extend((f16*)o, (const f16*)q, (const f16*)q_trans, transpose_out != 0, kv_data, kv_param, (const int*)kv_indptr,
+                                   (const int*)kv_indices, (const int*)last_page_offset, num_layers, layer_idx, num_cache_heads, q_group, copies,
+                                   q_len, page_size, head_dim, batch_size, (hipStream_t)stream, fp16_cache != 0);
     return check_launch(rc, what);
 }
 

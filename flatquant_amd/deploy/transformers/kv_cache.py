@@ -111,6 +111,16 @@ FUSE_APPEND_MAX_PAIRS = 1024
 # requests (256 pairs: one workgroup per CU either way), 125.1 / 136.1 / 127.5 at 64 (512), 195.7 / 203.2 / 199.3 at 128 (1024). With this
 # routing (second table there) rotate costs 3.1 / 5.6 us over no rope at 64 / 128 requests, 1.4 / 0.8 us above the one-launch form called directly. Launches of one or two query heads per workgroup keep their occupancy with rope and are not bounded here.
 ROPE_FUSE_MAX_FOUR_HEAD_WGS = 256
+# chunk extend: from this many tokens per request on, a step after the prompt (a follow-up prompt, a prompt fed in pieces) runs its attention on
+# ops.kv_chunk_extend (128 (token, head) rows per workgroup, every tile of the cache unpacked once for all of them) instead of ops.kv_batch_extend
+# (16 rows per workgroup). Measured on Llama-3-8B heads, INT4 pages, 2048 cached rows per request (profiles/kv_chunk_extend.txt; chunk / extend, us): the
+# new launch walks a request's rows in ONE workgroup per 128 (token, head) rows, so a launch never takes less than ~104 us at 2048 rows, and with few
+# requests the old launch's split over rows wins far longer — one request: 104.2 / 22.0 at T = 64, 104.6 / 25.5 at 128, 105.5 / 72.9 at 512, 117.3 / 243.0 at
+# 2048; 8 requests: 106.9 / 71.1 at 64, 110.5 / 125.5 at 128, 247.7 / 443.3 at 512; 64 requests: 138.9 / 131.0 at T = 16, 156.3 / 240.7 at 32, 295.2 / 459.2
+# at 64, 4602 / 15766 at 2048. T = 2048 is the one measured size from 64 up at which it wins at every measured batch (0.48 / 0.31 / 0.29x at 1 / 8 / 64
+# requests; 0.66x at one request over 8192 rows), so that is the constant; the crossover between 512 and 2048 at one request was not measured. With 8
+# requests and more the op itself pays from 128 tokens on (ops.kv_chunk_extend, called directly); a rule in requests x tokens is not built.
+EXTEND_CHUNK_MIN_TOKENS = 2048
 
 
 class MultiLayerPagedKVCache4Bit:
@@ -403,7 +413,8 @@ class MultiLayerPagedKVCache4Bit:
     def _extend_closure(self, added, args, layer_idx, had, tk_inv_t, copies, rope=None):
         """The attention of a step that appended ``added`` > 1 tokens per request (a speculative verify, a follow-up prompt, a prompt fed
         in pieces): the closure takes q [bsz, added, heads, head_dim] and runs causal attention over the cache — token t of the step sees
-        the rows before the step and the step's tokens 0 .. t (ops.kv_batch_extend, fq_kv_batch_extend)."""
+        the rows before the step and the step's tokens 0 .. t (ops.kv_batch_extend, fq_kv_batch_extend; from EXTEND_CHUNK_MIN_TOKENS tokens on,
+        at head_dim 128 with 1 / 2 / 4 / 8 query heads per set of cached rows: ops.kv_chunk_extend, fq_kv_chunk_extend)."""
         length_now = self.length
 
         def attend(q, transposed=False):
@@ -418,6 +429,11 @@ class MultiLayerPagedKVCache4Bit:
                 q2 = ops.hadamard(q2.contiguous())
             elif tk_inv_t is not None:
                 qt = self._as_f16(tk_inv_t)
+            cache_heads = args[0].shape[3]
+            q_group = copies if copies > 1 else (q2.shape[2] // cache_heads if q2.shape[2] % cache_heads == 0 else 0)
+            if (EXTEND_CHUNK_MIN_TOKENS is not None and added >= EXTEND_CHUNK_MIN_TOKENS
+                    and ops.kv_chunk_extend_supported(q_group, q2.shape[3])):
+                return ops.kv_chunk_extend(q2.contiguous(), *args, layer_idx, qt, transposed, kv_copies=copies)
             return ops.kv_batch_extend(q2.contiguous(), *args, layer_idx, qt, transposed, seq_hint=length_now, kv_copies=copies)
         return attend
 

@@ -1882,6 +1882,45 @@ def kv_batch_extend(q: torch.Tensor, kv_data: torch.Tensor, kv_param: torch.Tens
     return o
 
 
+def kv_chunk_extend(q: torch.Tensor, kv_data: torch.Tensor, kv_param: torch.Tensor, kv_indptr: torch.Tensor,
+                    kv_indices: torch.Tensor, last_page_offset: torch.Tensor, layer_idx: int,
+                    q_trans: Optional[torch.Tensor] = None, transpose_out: bool = False, kv_copies: int = 1) -> torch.Tensor:
+    """kv_batch_extend's attention for prompt-sized steps (fq_kv_chunk_extend): the same tensors, lengths, causal mask, heads, ``q_trans``,
+    ``transpose_out`` and ``kv_copies``, computed by a launch in the prompt attention's shape — a workgroup per (request, set of cached rows,
+    128 (token, head) rows of q), every 64-row tile of the cache unpacked once for all of them. No workspace and no split: two calls are
+    bit-identical, and a step fed as two consecutive calls equals the one call bit for bit. head_dim 128; 1, 2, 4 or 8 query heads per set of
+    cached rows (anything else: FqError, kv_batch_extend takes it)."""
+    _chk(q, "q"), _chk(kv_data, "kv_data", kv_data.dtype), _chk(kv_param, "kv_param")
+    n_layers, kv_heads, page_size, hd = _kv_geometry(kv_data)
+    batch = _chk_kv_index(kv_indptr, kv_indices, last_page_offset)
+    f16_cache = kv_data.dtype == torch.float16
+    if q.dim() != 4 or q.shape[0] != batch or q.shape[3] != hd or q.shape[1] < 1 or q.shape[2] % kv_heads:
+        raise ValueError(f"q must be [{batch}, q_len >= 1, a multiple of {kv_heads}, {hd}]")
+    q_len, heads = q.shape[1], q.shape[2]
+    q_group = heads // kv_heads
+    if kv_copies > 1:
+        if q_group != 1 or kv_heads % kv_copies or kv_copies > 8:
+            raise ValueError(f"kv_copies={kv_copies}: needs a replicated cache (query heads == cache heads == {kv_heads}) in groups of at most 8")
+        q_group = kv_copies
+    if q_trans is not None:
+        _chk(q_trans, "q_trans")
+        if q_trans.shape != (hd, hd):
+            raise ValueError("q_trans must be [head_dim, head_dim]")
+    o = torch.empty((batch, q_len, hd, heads) if transpose_out else (batch, q_len, heads, hd), dtype=torch.float16, device=q.device)
+    if batch == 0:
+        return o
+    with _on(q.device):
+        check(lib.fq_kv_chunk_extend(1 if f16_cache else 0, _ptr(o), _ptr(q), _ptr(q_trans), 1 if transpose_out else 0, _ptr(kv_data),
+                                     _ptr(kv_param), _ptr(kv_indptr), _ptr(kv_indices), _ptr(last_page_offset), n_layers, layer_idx,
+                                     kv_heads, q_group, kv_copies, q_len, page_size, hd, batch, _stream(q)))
+    return o
+
+
+def kv_chunk_extend_supported(q_group: int, head_dim: int) -> bool:
+    """Does fq_kv_chunk_extend take ``q_group`` query heads per set of cached rows at this head_dim? (What the cache class asks before it routes.)"""
+    return head_dim == 128 and q_group in (1, 2, 4, 8)
+
+
 def prefill_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_trans: Optional[torch.Tensor] = None,
                       seq_start: Optional[torch.Tensor] = None, seq_len: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Causal self-attention of a prompt (fq_prefill_attention_f16): q [batch, seq, q_heads, 128], k / v [batch, seq, kv_heads, 128] fp16 -> o

@@ -713,6 +713,19 @@ int fq_kv_batch_extend(int fp16_cache, void* o, const void* q, const void* q_tra
                        int layer_idx, int num_cache_heads, int q_group, int copies, int q_len, int page_size, int head_dim, int batch_size,
                        int seq_hint, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* PROMPT-SIZED STEPS OVER THE CACHE: fq_kv_batch_extend's contract — the same tensors, lengths, causal mask, head conventions (q_group, copies),
+ * de-quantiser, q_trans and transpose_out; FlashInfer's append attention over a paged cache, include/flashinfer/prefill.cuh — as a launch
+ * in the shape of fq_prefill_attention_f16: a workgroup owns one set of cached rows and 128 (token, head) rows of q, every 64-row tile of the
+ * cache is unpacked once per 128 of them (fq_kv_batch_extend: once per 16). It is the launch for a follow-up prompt or a prompt fed in pieces;
+ * fq_kv_batch_extend remains the one for a verify step of a few tokens. No workspace, no seq_hint, no split over rows, no atomics: two
+ * launches are bit-identical, and a step fed as two consecutive launches (the first with index tensors that describe the shorter length)
+ * equals the one launch bit for bit. Rows 0 .. L_b - 1 of a request are assumed finite; rows at or beyond L_b are never read.
+ *   head_dim 128 (64 / 96: FQ_EUNSUPPORTED); q_group 1, 2, 4 or 8 (any other: FQ_EUNSUPPORTED); any page_size >= 1; q_len < 1, a bad layer
+ *   index, copies > 8, copies not dividing q_group or num_cache_heads: FQ_EINVAL. o, q, kv_data, q_trans 16-byte aligned. */
+int fq_kv_chunk_extend(int fp16_cache, void* o, const void* q, const void* q_trans, int transpose_out, const void* kv_data, const void* kv_param,
+                       const void* kv_indptr, const void* kv_indices, const void* last_page_offset, int num_layers, int layer_idx,
+                       int num_cache_heads, int q_group, int copies, int q_len, int page_size, int head_dim, int batch_size, void* stream);
+
 /* THE PROMPT'S OWN ATTENTION: causal flash-style self-attention over the un-quantised (transformed) states the cache returns on its first call
  * per layer — what the reference hands to flash-attn (deploy/transformers/modeling_llama.py:125-137: transformers' _flash_attention_forward(
  * query_states @ trans_matrix_k_inv_t, key_states, value_states, query_length, attention_mask, is_causal=True)).
