@@ -83,11 +83,14 @@ __device__ __forceinline__ unsigned kv_q1(f16 x, KvParams p) {
 // zero point (an integer <= 15 with lac) is added to that sum exactly, the clamp to [0, 15] is a packed max / min against
 // 1536 / 1551, and the digit is the low nibble of each half. Quotients beyond +-512 leave the exact range of the magic add
 // on the side they are clamped to. Without lac the zero point (-xmin, not an integer) is added BEFORE the division
-// (kv_cache.py:36-43), a packed fp16 add.
+// (kv_cache.py:36-43), a packed fp16 add; there the quotient is never negative and only the upper bound is applied (below).
+// An Inf scale (a row whose range overflows fp16) is taken as FLT_MAX: r = 0 then gives the quotient 0 of finite / Inf instead of the
+// NaN of the residual's 0 * Inf, which the packed min would turn into digit 15.
 template <bool LAC>
 __device__ __forceinline__ unsigned kv_q8(uint32_t xa, uint32_t xb, uint32_t xc, uint32_t xd, float r, float s, uint32_t zero2) {
     uint32_t ha, hb, hc, hd;
     float t0, t1, e0, e1;
+    s = __builtin_fminf(s, 3.40282347e+38f);
     if (!LAC)
         asm("v_pk_add_f16 %0, %0, %4\n\tv_pk_add_f16 %1, %1, %4\n\tv_pk_add_f16 %2, %2, %4\n\tv_pk_add_f16 %3, %3, %4"
             : "+v"(xa), "+v"(xb), "+v"(xc), "+v"(xd)
@@ -118,8 +121,16 @@ __device__ __forceinline__ unsigned kv_q8(uint32_t xa, uint32_t xb, uint32_t xc,
             : "v"(zero2));
     uint32_t d, p1, p2, u1, u2;
     const uint32_t sel = 0x06040200u;      // bytes 0 and 2 of the second source, then of the first
-    // lac only: without it (x + zero) / scale lies in [0, 15] by construction (x + zero <= fp16(xmax - xmin) = 15 scale
-    // up to 2^-11, and >= fp16(xmin - xmin) = 0; the 1e-5 floor only makes the quotients smaller)
+    // Without lac (x + zero) / scale is >= fp16(xmin - xmin) = 0, so the lower bound is lac's alone. The upper bound is NOT implied:
+    // x + zero <= fp16(xmax - xmin) = 15 scale holds up to the rounding of scale = fp16(d / 15), which is 2^-11 only while the scale is a
+    // normal number. Below d ~ 9.2e-4 it is subnormal and ranges of 171, 172, 186, 187, 202, 217 .. units of 2^-24 (just above the 1e-5
+    // floor) give the row's maximum the quotient 15.5 .. 15.63: 1536 + 16 = 0x6610, whose low nibble is 0 — the largest value stored as the
+    // smallest (tests/test_gpu_kv_edge_rows.py). The reference clamps to [0, 15] in both modes (kv_cache.py:43).
+    if (!LAC)
+        asm("v_pk_min_f16 %[ha], %[ha], %[hi]\n\tv_pk_min_f16 %[hb], %[hb], %[hi]\n\t"
+            "v_pk_min_f16 %[hc], %[hc], %[hi]\n\tv_pk_min_f16 %[hd], %[hd], %[hi]"
+            : [ha] "+v"(ha), [hb] "+v"(hb), [hc] "+v"(hc), [hd] "+v"(hd)
+            : [hi] "v"(hi2));
     if (LAC)
         asm("v_pk_max_f16 %[ha], %[ha], %[mg]\n\tv_pk_max_f16 %[hb], %[hb], %[mg]\n\t"
             "v_pk_max_f16 %[hc], %[hc], %[mg]\n\tv_pk_max_f16 %[hd], %[hd], %[mg]\n\t"
