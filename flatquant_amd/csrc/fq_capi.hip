@@ -746,7 +746,7 @@ int fq_int4_gemm_i32(const void* x, const void* w, int64_t M, int N, int K, void
     if (M == 0) return FQ_OK;
     const int rc = fq_launch_gemm_i4((const uint8_t*)x, (const uint8_t*)w, M, N, K, (int32_t*)c, nullptr, nullptr, nullptr,
                                      nullptr, (hipStream_t)stream);
-    if (rc == -1000) return fail(FQ_EUNSUPPORTED, "fq_int4_gemm_i32: shape M=%lld N=%d K=%d not supported", (long long)M, N, K);
+    if (rc == -1000) return fail(FQ_EUNSUPPORTED, "fq_int4_gemm_i32: shape M=%lld N=%d K=%d not supported (K < 2^25)", (long long)M, N, K);
     return check_launch(rc, "fq_int4_gemm_i32");
 }
 
@@ -759,7 +759,7 @@ int fq_int4_linear_f16(const void* x, const void* x_scale, const void* w, const 
     if (M == 0) return FQ_OK;
     const int rc = fq_launch_gemm_i4((const uint8_t*)x, (const uint8_t*)w, M, N, K, nullptr, (f16*)y, (const f16*)x_scale,
                                      (const f16*)w_scale, (const f16*)bias, (hipStream_t)stream);
-    if (rc == -1000) return fail(FQ_EUNSUPPORTED, "fq_int4_linear_f16: shape M=%lld N=%d K=%d not supported", (long long)M, N, K);
+    if (rc == -1000) return fail(FQ_EUNSUPPORTED, "fq_int4_linear_f16: shape M=%lld N=%d K=%d not supported (K < 2^25)", (long long)M, N, K);
     return check_launch(rc, "fq_int4_linear_f16");
 }
 
@@ -778,7 +778,7 @@ int fq_int4_skinny_gemm_i32(const void* x, const void* w_image, int64_t M, int N
     if (!x || !w_image || !c) return fail(FQ_EINVAL, "fq_int4_skinny_gemm_i32: NULL pointer");
     const int rc = fq_launch_gemm_i4_skinny((const uint8_t*)x, w_image, M, N, K, (int32_t*)c, nullptr, nullptr, nullptr, nullptr,
                                             (hipStream_t)stream);
-    if (rc == -1000) return fail(FQ_EUNSUPPORTED, "fq_int4_skinny_gemm_i32: M=%lld K=%d (M <= 128, K %% 64 == 0)", (long long)M, K);
+    if (rc == -1000) return fail(FQ_EUNSUPPORTED, "fq_int4_skinny_gemm_i32: M=%lld K=%d (M <= 128, K %% 64 == 0, K < 131072)", (long long)M, K);
     return check_launch(rc, "fq_int4_skinny_gemm_i32");
 }
 
@@ -789,7 +789,7 @@ int fq_int4_skinny_linear_f16(const void* x, const void* x_scale, const void* w_
     if (!x || !w_image || !y || !x_scale || !w_scale) return fail(FQ_EINVAL, "fq_int4_skinny_linear_f16: NULL pointer");
     const int rc = fq_launch_gemm_i4_skinny((const uint8_t*)x, w_image, M, N, K, nullptr, (f16*)y, (const f16*)x_scale,
                                             (const f16*)w_scale, (const f16*)bias, (hipStream_t)stream);
-    if (rc == -1000) return fail(FQ_EUNSUPPORTED, "fq_int4_skinny_linear_f16: M=%lld K=%d (M <= 128, K %% 64 == 0)", (long long)M, K);
+    if (rc == -1000) return fail(FQ_EUNSUPPORTED, "fq_int4_skinny_linear_f16: M=%lld K=%d (M <= 128, K %% 64 == 0, K < 131072)", (long long)M, K);
     return check_launch(rc, "fq_int4_skinny_linear_f16");
 }
 
@@ -810,7 +810,7 @@ int fq_int4_skinny_linear_split_f16(const void* x, const void* x_scale, const vo
         return fail(FQ_EINVAL, "%s: workspace of %lld bytes, fq_int4_skinny_split_workspace_bytes says %lld", what, (long long)workspace_bytes, (long long)need);
     const int rc = fq_launch_gemm_i4_skinny_split((const uint8_t*)x, w_image, M, N, K, (f16*)y, (const f16*)x_scale, (const f16*)w_scale, (const f16*)bias,
                                                   need > 0 ? (int*)workspace : nullptr, (hipStream_t)stream);
-    if (rc == -1000) return fail(FQ_EUNSUPPORTED, "%s: M=%lld K=%d (M <= 128, K %% 64 == 0)", what, (long long)M, K);
+    if (rc == -1000) return fail(FQ_EUNSUPPORTED, "%s: M=%lld K=%d (M <= 128, K %% 64 == 0, K < 131072)", what, (long long)M, K);
     return check_launch(rc, what);
 }
 
@@ -828,7 +828,7 @@ int fq_int4_skinny_linear_multi_f16(int n, const void* const* x, const void* con
     if (M == 0) return FQ_OK;
     const int rc = fq_launch_gemm_i4_skinny_multi(n, (const uint8_t* const*)x, w_image, M, N, K, (f16* const*)y, (const f16* const*)x_scale,
                                                   (const f16* const*)w_scale, (const f16* const*)bias, (hipStream_t)stream);
-    if (rc == -1000) return fail(FQ_EUNSUPPORTED, "%s: M=%lld K=%d (M <= 128, K %% 64 == 0)", what, (long long)M, K);
+    if (rc == -1000) return fail(FQ_EUNSUPPORTED, "%s: M=%lld K=%d (M <= 128, K %% 64 == 0, K < 131072)", what, (long long)M, K);
     return check_launch(rc, what);
 }
 

@@ -7,8 +7,9 @@
 // gfx950 has no INT4 matrix instruction; v_mfma_i32_32x32x32_i8 takes signed bytes. A nibble left in the HIGH half of
 // its byte IS the signed byte 16*q, so unpacking is one AND for the odd elements and shift + AND for the even ones
 // (3 VALU per packed dword, single-width: they issue in the shadow of the MFMAs), every product is 256*x*w and the
-// accumulator is shifted right by 8 at the end (exact; |sum| < 2^31 for K <= 131072). No sign-extension
-// arithmetic, no zero-point correction terms.
+// accumulator is shifted right by 8 at the end (exact while |sum| = 256 * 64 * K < 2^31, i.e. K < 131072: all -8 x -8 at
+// K = 131072 sums to exactly 2^31 and wraps — the launchers keep the int8 path below that K, see FQ_I8_K_LIMIT). No
+// sign-extension arithmetic, no zero-point correction terms.
 //
 // Tiling: 256 x 256 output tile per 8-wave workgroup, K in steps of 128 nibbles (64 bytes per row), three LDS stages of
 // 32 KB filled by LDS-DMA (16 rows x 64 bytes per instruction, 16-byte pieces XOR-swizzled by (row>>2)&3 on the source
@@ -26,6 +27,11 @@ typedef int i32x16 __attribute__((ext_vector_type(16)));
 typedef __attribute__((address_space(3))) void lds_void_g;
 
 constexpr int BM = 256, BN = 256;     // output tile (tokens x output features)
+// The accumulators' ranges, as the launchers enforce them (every INT4 product is at most 64 in magnitude):
+//   int8 matrix path (tile and weight-streaming kernels): products carry 256 — 256 * 64 * K < 2^31 needs K < 2^17;
+//   general-shape kernel: unscaled products in an int32 — 64 * K < 2^31 needs K < 2^25.
+constexpr int FQ_I8_K_LIMIT = 1 << 17;       // the first K the int8 path does not take
+constexpr int FQ_SIMPLE_K_LIMIT = 1 << 25;   // the first K no kernel of this file takes
 constexpr int BKB = 64;               // packed bytes of K per stage and row (128 nibbles = 4 MFMA K-steps)
 #ifndef FQ_GEMM_STAGES
 #define FQ_GEMM_STAGES 3   // LDS stages of 32 KB, all of them in flight or being read
@@ -221,8 +227,9 @@ __global__ __launch_bounds__(GT) void fq_gemm_i4_kernel(const uint8_t* __restric
     }
 }
 
-// Any other shape the reference accepts (K % 32 == 0, deploy/__init__.py:38): one thread per output element,
-// 32-bit loads of 8 nibbles, sign extension by shifts. Correct, not fast; the model shapes never get here.
+// Any other shape the reference accepts (K % 32 == 0, deploy/__init__.py:38), and every K from FQ_I8_K_LIMIT up: one thread per
+// output element, 32-bit loads of 8 nibbles, sign extension by shifts, products added UNSCALED (exact for K < FQ_SIMPLE_K_LIMIT).
+// Correct, not fast; the model shapes never get here.
 __global__ __launch_bounds__(256) void fq_gemm_i4_simple_kernel(const uint8_t* __restrict__ X, const uint8_t* __restrict__ W,
                                                                int M, int N, int Kb, GemmOut out) {
     const int64_t total = (int64_t)M * N;
@@ -397,17 +404,17 @@ __global__ __launch_bounds__(SK_WAVES * 64) void fq_gemm_i4_skinny_kernel(const 
 
 }  // namespace
 
-// -1000: shape not accepted (K must be a multiple of 32, as deploy.matmul asserts).
+// -1000: shape not accepted (K must be a multiple of 32, as deploy.matmul asserts, and below 2^25: a full-scale sum must fit the int32).
 int fq_launch_gemm_i4(const uint8_t* X, const uint8_t* W, int64_t M, int N, int K, int32_t* c, f16* y, const f16* srow,
                       const f16* scol, const f16* bias, hipStream_t stream) {
-    if ((K & 31) || K < 32 || M < 1 || N < 1 || M > (1 << 30)) return -1000;
+    if ((K & 31) || K < 32 || K >= FQ_SIMPLE_K_LIMIT || M < 1 || N < 1 || M > (1 << 30)) return -1000;
     GemmOut o;
     o.c = c;
     o.y = y;
     o.srow = srow;
     o.scol = scol;
     o.bias = bias;
-    if ((K & 127) || (N & 15)) {
+    if ((K & 127) || (N & 15) || K >= FQ_I8_K_LIMIT) {   // (the tile kernel's accumulator is 256 x the sum: it would wrap at K = 2^17)
         int64_t blocks = (M * (int64_t)N + 255) / 256;
         if (blocks > 65536) blocks = 65536;
         hipLaunchKernelGGL(fq_gemm_i4_simple_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, X, W, (int)M, N, K / 2, o);
@@ -432,10 +439,10 @@ int fq_launch_i4_to_frag(const uint8_t* W, int N, int K, void* img, int n_cu, hi
     return (int)hipGetLastError();
 }
 
-// -1000: M > 128 or K % 64 != 0 (use the tile kernel)
+// -1000: M > 128, K % 64 != 0 or K >= 2^17 (the accumulator carries 256 x the sum; use fq_launch_gemm_i4)
 int fq_launch_gemm_i4_skinny(const uint8_t* X, const void* wimg, int64_t M, int N, int K, int32_t* c, f16* y, const f16* srow,
                              const f16* scol, const f16* bias, hipStream_t stream) {
-    if (M < 1 || M > 128 || N < 1 || (K & 63) || K < 64 || K > 131072) return -1000;
+    if (M < 1 || M > 128 || N < 1 || (K & 63) || K < 64 || K >= FQ_I8_K_LIMIT) return -1000;
     GemmOut o;
     o.c = c;
     o.y = y;
@@ -459,7 +466,7 @@ int fq_launch_gemm_i4_skinny(const uint8_t* X, const void* wimg, int64_t M, int 
 // range is long; at least two rounds of blobs per workgroup of a split (measured: profiles/r06_skinny_ksplit.txt).
 int fq_gemm_i4_skinny_splits(int64_t M, int N, int K) {
     const int tiles = (N + 31) / 32, KB = K / 64;
-    if (M < 1 || M > 128 || tiles > 128 || (K & 63)) return 1;
+    if (M < 1 || M > 128 || tiles > 128 || (K & 63) || K >= FQ_I8_K_LIMIT) return 1;   // (K >= 2^17: the plain launcher refuses it)
     // up to 32 rows (one token tile: the launch is latency-, not arithmetic-bound) only a long K range pays for the hand-over: measured on a 4096-wide
     // projection (r06c69) K = 14336: 8.5 -> 8.8 us at one row, 11.2 -> 9.4 at 16, 15.8 -> 11.3 at 32; K = 28672: 16.6 -> 13.3 at one row, 30.6 -> 18.5 at 32
     if (M < 33 && (K < 8192 || (M < 9 && K < 16384))) return 1;
@@ -496,10 +503,10 @@ int fq_launch_gemm_i4_skinny_split(const uint8_t* X, const void* wimg, int64_t M
     return (int)hipGetLastError();
 }
 
-// -1000: n not in 1..4, M > 128 or K % 64 != 0
+// -1000: n not in 1..4, M > 128, K % 64 != 0 or K >= 2^17
 int fq_launch_gemm_i4_skinny_multi(int n, const uint8_t* const* X, const void* const* wimg, int64_t M, const int* N, int K, f16* const* y,
                                    const f16* const* srow, const f16* const* scol, const f16* const* bias, hipStream_t stream) {
-    if (n < 1 || n > 4 || M < 1 || M > 128 || (K & 63) || K < 64 || K > 131072) return -1000;
+    if (n < 1 || n > 4 || M < 1 || M > 128 || (K & 63) || K < 64 || K >= FQ_I8_K_LIMIT) return -1000;
     SkinnyProblems pr = {};
     pr.n = n;
     int tiles = 0;

@@ -1397,8 +1397,11 @@ def int4_to_frag(w: torch.Tensor) -> torch.Tensor:
     return img
 
 
+SKINNY_K_LIMIT = 131072      # the weight-streaming kernel's accumulator carries 256 x the sum: all -8 x -8 would wrap at this K
+
+
 def skinny_supported(M: int, K: int) -> bool:
-    return 1 <= M <= 128 and K % 64 == 0
+    return 1 <= M <= 128 and K % 64 == 0 and K < SKINNY_K_LIMIT
 
 
 def int4_skinny_matmul(x: torch.Tensor, w_image: torch.Tensor, N: int) -> torch.Tensor:

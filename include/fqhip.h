@@ -341,7 +341,8 @@ int fq_block_quant_bf16(const void* x, const void* P, int64_t rows, int R, int C
  * INT4 x INT4 -> INT32 GEMM on packed nibbles (deploy/kernels/gemm.cu:8-47 behind deploy.matmul,
  * deploy/__init__.py:37-41):  c[m][n] = sum_k x[m][k] * w[n][k].
  *   x [M, K/2] uint8 (packed activations, e.g. PackedQuantizedTensor.quantized_x), w [N, K/2] uint8 (Linear4bit.weight),
- *   low nibble = even k, two's complement;  c [M, N] int32.  K % 32 == 0 (the reference's assert).
+ *   low nibble = even k, two's complement;  c [M, N] int32.  K % 32 == 0 (the reference's assert) and K < 2^25 (a full-scale sum,
+ *   64 K, must fit the int32: FQ_EUNSUPPORTED beyond). K >= 2^17 runs the general-shape kernel (the matrix path carries 256 x the sum).
  */
 int fq_int4_gemm_i32(const void* x, const void* w, int64_t M, int N, int K, void* c, void* stream);
 
@@ -361,7 +362,8 @@ int fq_int4_linear_f16(const void* x, const void* x_scale, const void* w, const 
  *   fq_int4_frag_bytes(N, K)                 bytes of the image (K % 64 == 0; -1 otherwise)
  *   fq_int4_to_frag(w [N, K/2], N, K, image)
  *   fq_int4_skinny_gemm_i32 / fq_int4_skinny_linear_f16: as fq_int4_gemm_i32 / fq_int4_linear_f16 with the image in
- *   place of w; M <= 128, K % 64 == 0, FQ_EUNSUPPORTED otherwise. Bit-identical results.
+ *   place of w; M <= 128, K % 64 == 0, K < 2^17 (131072: the accumulator carries 256 x the sum), FQ_EUNSUPPORTED otherwise — the split and
+ *   multi-problem launches below alike. Bit-identical results.
  */
 int64_t fq_int4_frag_bytes(int N, int K);
 int fq_int4_to_frag(const void* w, int N, int K, void* image, void* stream);
