@@ -65,7 +65,7 @@ int fq_launch_kv_decode(f16* o, const f16* q, void* kv_data, void* kv_param, con
                         int num_layers, int layer_idx, int num_heads, int page_size, int head_dim, int batch, const f16* qt,
                         int transpose_out, hipStream_t stream, bool f16_cache = false, float* ws = nullptr, int splits = 1, int qgroup = 1,
                         const f16* k_new = nullptr, const f16* v_new = nullptr, const void* t_image = nullptr, int src_heads = 1, int copies = 1,
-                        const f16* rope_cos = nullptr, const f16* rope_sin = nullptr);
+                        const f16* rope_cos = nullptr, const f16* rope_sin = nullptr, bool had = false, float had_scale = 0.0f);
 int fq_launch_rope(f16* q_out, f16* k_out, const f16* q, const f16* k, const f16* cos, const f16* sin, int64_t tokens, int q_heads, int k_heads,
                    int head_dim, hipStream_t stream);
 int64_t fq_kv_timage_bytes(int hd);
@@ -1275,12 +1275,13 @@ int fq_kv_transform_image_f16(const void* trans, int head_dim, void* image, void
     return check_launch(fq_launch_kv_timage((const f16*)trans, head_dim, image, (hipStream_t)stream), "fq_kv_transform_image_f16");
 }
 
-// fq_kv_decode_append_i4 and fq_kv_decode_append_rope_i4 (cos / sin: the step's rotary tables, both or neither)
+// fq_kv_decode_append_i4, fq_kv_decode_append_rope_i4 (cos / sin: the step's rotary tables, both or neither) and fq_kv_decode_append_had_i4 (had: the launch
+// rotates its queries and the new K row by the normalised Hadamard matrix, had_scale = 1 / sqrt(head_dim); its callers pass no q_trans, image or tables)
 static int kv_decode_append(const char* what, void* o, const void* q, const void* q_trans, int transpose_out, const void* k_new, const void* v_new,
                             const void* k_trans_image, int src_heads, const void* kv_data, const void* kv_param, const void* kv_indptr,
                             const void* kv_indices, const void* last_page_offset, int num_layers, int layer_idx, int num_kv_heads, int q_group,
                             int page_size, int head_dim, int batch_size, int seq_hint, int read_one_copy, void* workspace, int64_t workspace_bytes, void* stream,
-                            const void* cos, const void* sin) {
+                            const void* cos, const void* sin, bool had = false, float had_scale = 0.0f) {
     int rc = kv_geometry_ok(what, num_layers, layer_idx, num_kv_heads, page_size, head_dim, batch_size);
     if (rc != FQ_OK) return rc;
     if (q_group < 1 || q_group > 64) return fail(FQ_EINVAL, "%s: q_group=%d out of [1, 64]", what, q_group);
@@ -1304,7 +1305,7 @@ static int kv_decode_append(const char* what, void* o, const void* q, const void
     rc = fq_launch_kv_decode((f16*)o, (const f16*)q, (void*)kv_data, (void*)kv_param, (const int*)kv_indptr, (const int*)kv_indices,
                              (const int*)last_page_offset, num_layers, layer_idx, q_heads, page_size, head_dim, batch_size,
                              (const f16*)q_trans, transpose_out != 0, (hipStream_t)stream, false, (float*)workspace, splits, share,
-                             (const f16*)k_new, (const f16*)v_new, k_trans_image, src_heads, copies, (const f16*)cos, (const f16*)sin);
+                             (const f16*)k_new, (const f16*)v_new, k_trans_image, src_heads, copies, (const f16*)cos, (const f16*)sin, had, had_scale);
     return check_launch(rc, what);
 }
 
@@ -1325,6 +1326,15 @@ int fq_kv_decode_append_rope_i4(void* o, const void* q, const void* q_trans, int
     return kv_decode_append("fq_kv_decode_append_rope_i4", o, q, q_trans, transpose_out, k_new, v_new, k_trans_image, src_heads, kv_data, kv_param, kv_indptr,
                             kv_indices, last_page_offset, num_layers, layer_idx, num_kv_heads, q_group, page_size, head_dim, batch_size, seq_hint,
                             read_one_copy, workspace, workspace_bytes, stream, cos, sin);
+}
+
+int fq_kv_decode_append_had_i4(void* o, const void* q, int transpose_out, const void* k_new, const void* v_new, int src_heads, const void* kv_data,
+                               const void* kv_param, const void* kv_indptr, const void* kv_indices, const void* last_page_offset, int num_layers, int layer_idx,
+                               int num_kv_heads, int q_group, int page_size, int head_dim, int batch_size, int seq_hint, int read_one_copy, void* workspace,
+                               int64_t workspace_bytes, void* stream, float had_scale) {
+    return kv_decode_append("fq_kv_decode_append_had_i4", o, q, nullptr, transpose_out, k_new, v_new, nullptr, src_heads, kv_data, kv_param, kv_indptr,
+                            kv_indices, last_page_offset, num_layers, layer_idx, num_kv_heads, q_group, page_size, head_dim, batch_size, seq_hint,
+                            read_one_copy, workspace, workspace_bytes, stream, nullptr, nullptr, true, had_scale);
 }
 
 int fq_rope_f16(void* q_out, void* k_out, const void* q, const void* k, const void* cos, const void* sin, int64_t tokens, int q_heads, int k_heads,

@@ -31,6 +31,7 @@
 //     instructions per 16-row step where the scalar kernel had ~300), 8 x 8192: 108 -> 46 us (0.77), 128 x 4096: 0.74, one request x 2048:
 //     20.8 -> 8.6 us (profiles/r05_kvdecode_timing.txt, r05_kvdecode_pmc.txt).
 #include "fq_kv_common.hpp"
+#include "fq_xlane.hpp"
 #include <type_traits>
 
 namespace {
@@ -48,6 +49,8 @@ struct KvNew {
     const f16* v;        // ... values
     const uint4* timg;   // the K transform as the fragment image fq_kv_transform_image_f16 wrote (32 KB at head_dim 128), or nullptr: no transform
     int src_heads;       // heads of k / v: cache head c is a copy of source head c / (cache heads / src_heads) (kv_cache.py:286-296)
+    float had_scale;     // APPEND == 3 (fq_kv_decode_append_had_i4): the fp32 factor of the normalised Hadamard rotation, 1 / sqrt(head_dim) as the caller computed it
+                         // (in what was the padding in front of `cos`: the kernel arguments of every other instantiation stay as they were)
     const f16* cos;      // [batch, head_dim] fp16 rotary tables of the step (fq_kv_decode_append_rope_i4), or nullptr: no rotary embedding. With them the
     const f16* sin;      // launch rotates its queries and the new K row first (fqkv::kv_rope1: the three fp16 roundings of apply_rotary_pos_emb); V never
 };
@@ -199,10 +202,16 @@ __device__ __forceinline__ float* kv_states(float* ws, size_t pairs) { return ws
 // value and not a runtime pointer of the APPEND instantiations: as a pointer it cost those up to nine VGPRs and two SGPRs; so every instantiation
 // that was there before keeps its code, registers and spills. The four-head form with rotary embedding is NOT held to 128 VGPRs (132, three waves
 // per SIMD): held, it spills four to five registers like its siblings, and nothing new may spill (tests/test_host_cpu.py).
+// 3: append + the normalised HADAMARD rotation over head_dim of the queries and of the new K row (fq_kv_decode_append_had_i4; kv_cache.py:134-138,265-266 with
+// trans="had", the reference's default cache): fq_hadamard_f16's arithmetic for rows of 128 to the bit — fp32 butterflies in ascending stride order, one fp32
+// product with the scale, one rounding to fp16 — so cache bytes, parameters and output equal ops.hadamard on q and k followed by APPEND == 1. No q_trans, no image.
+// Its four-head form is not held to 128 VGPRs either: held, it spills three registers.
 template <int HD, int NW, bool UNI, bool F16, bool SPLIT, int QG = 1, int APPEND = 0>
-__global__ __launch_bounds__(NW * 64, (KV_PVM_OCC4 && KV_PV_MFMA && QG == 4 && !F16 && UNI && APPEND != 2) ? 4 : 2) void fq_kv_decode_kernel(f16* __restrict__ o, const f16* __restrict__ q, PagedKv p,
+__global__ __launch_bounds__(NW * 64, (KV_PVM_OCC4 && KV_PV_MFMA && QG == 4 && !F16 && UNI && APPEND < 2) ? 4 : 2) void fq_kv_decode_kernel(f16* __restrict__ o, const f16* __restrict__ q, PagedKv p,
                                                                const f16* __restrict__ qt, int transpose_out, float* ws, int qgroup, KvNew nw) {
-    constexpr bool ROPE = APPEND == 2;
+    constexpr bool ROPE = APPEND == 2, HAD = APPEND == 3;
+    constexpr bool PRE = ROPE || HAD;  // the queries (s_q) and the new K row (s_krot) are rewritten in LDS in front of everything else
+    if constexpr (HAD) qt = nullptr;   // (no query transform behind the rotation: the branches on it fold away)
     constexpr int QL = HD / 32;        // lanes per cached row: 4 for head_dim 128, 2 for 64
     constexpr int RPW = 64 / QL;       // rows per wave and step: the N of the MFMA (16 / 32)
     constexpr int NS = NW * RPW;       // partial softmax states per workgroup
@@ -246,6 +255,29 @@ __global__ __launch_bounds__(NW * 64, (KV_PVM_OCC4 && KV_PV_MFMA && QG == 4 && !
             const f16 y = fqkv::kv_rope1(x, j < HD / 2 ? -xp : xp, cs[j], sn[j]);
             if (g < QG) s_q[idx] = (float)y;
             else s_krot[j] = y;
+        }
+        __syncthreads();
+    }
+    // HAD (fq_kv_decode_append_had_i4): the same two places, written by the 128-point rotation. One wave per row: lane l holds elements 2 l and 2 l + 1, stride 1 is
+    // the pair in registers, strides 2 .. 64 are the six cross-lane stages of the standalone launch (xlane<6>: partner = lane ^ 1 .. 32, the element whose stride
+    // bit is clear is the minuend) — oracle.fq_oracle.hadamard's order of fp32 sums. Then fp16(fp32(v * scale)), fq_hadamard_reg.hip's to_f16 expression.
+    if constexpr (HAD) {
+        const bool own_k = seq_len > 0 && (!SPLIT || (int)((((seq_len - 1) / RPW) % ((int)gridDim.z * NW)) / NW) == (int)blockIdx.z);
+        const f16* q0 = q + ((size_t)b * QH + head) * HD;
+        const f16* k0 = nw.k + ((size_t)b * nw.src_heads + chead / (p.num_heads / nw.src_heads)) * HD;
+        const XMask xk(lane);
+        const int rows = own_k ? QG + 1 : QG;               // (workgroup-uniform; a wave's trips are wave-uniform: the cross-lane stages want every lane)
+        for (int g = wave; g < rows; g += NW) {
+            const f16x2 x2 = reinterpret_cast<const f16x2*>(g < QG ? q0 + g * HD : k0)[lane];
+            const float x0 = (float)x2[0], x1 = (float)x2[1];
+            const float y0 = xlane<6>(x0 + x1, xk), y1 = xlane<6>(x0 - x1, xk);
+            const f16 h0 = fq_mul_to_f16(y0, nw.had_scale), h1 = fq_mul_to_f16(y1, nw.had_scale);
+            if (g < QG) {
+                s_q[g * HD + 2 * lane] = (float)h0;
+                s_q[g * HD + 2 * lane + 1] = (float)h1;
+            } else {
+                reinterpret_cast<f16x2*>(s_krot)[lane] = f16x2{h0, h1};
+            }
         }
         __syncthreads();
     }
@@ -307,7 +339,7 @@ __global__ __launch_bounds__(NW * 64, (KV_PVM_OCC4 && KV_PV_MFMA && QG == 4 && !
                 for (int cc = 0; cc < NCHQ; ++cc) t += s_o[cc][tid];
                 s_q[g * HD + tid] = (float)(f16)t;
             }
-        } else if (!ROPE) {     // (ROPE: s_q holds the rotated query already)
+        } else if (!PRE) {     // (ROPE / HAD: s_q holds the rotated query already)
             for (int j = tid; j < HD; j += NW * 64) s_q[g * HD + j] = (float)qrow[j];
         }
         __syncthreads();
@@ -341,7 +373,7 @@ __global__ __launch_bounds__(NW * 64, (KV_PVM_OCC4 && KV_PV_MFMA && QG == 4 && !
 
     // APPEND: the new row (see KvNew). s_new (behind every other LDS array): [0..15] the K row's dwords, [16..31] the V row's, [32] / [33] the
     // (scale, zero) pairs, [36..] the per-wave extrema of the prologue.
-    // With rotary tables: [64..127] the rotated K row (s_krot above).
+    // With rotary tables or the Hadamard rotation: [64..127] the rotated K row (s_krot above).
     uint32_t* s_new = reinterpret_cast<uint32_t*>(kv_smem + NEW_OFF);
     const int64_t last_row = seq_len - 1;
     bool own = false;    // (workgroup-uniform) this workgroup's rows include last_row
@@ -359,7 +391,7 @@ __global__ __launch_bounds__(NW * 64, (KV_PVM_OCC4 && KV_PV_MFMA && QG == 4 && !
             const int h = lane >> 5;
             f16 kv16[2][16];   // [k, v][r]: feature 32 wave + 16 h + r of the (transformed) row — the columns lane (h, .) of fq_kv_quant_kernel's wave ends with
             if (wave < 4) {
-                if (nw.timg != nullptr) {
+                if (!HAD && nw.timg != nullptr) {
                     f16x8 xf[8], tf[8];
 #pragma unroll
                     for (int s = 0; s < 8; ++s) {
@@ -377,7 +409,7 @@ __global__ __launch_bounds__(NW * 64, (KV_PVM_OCC4 && KV_PV_MFMA && QG == 4 && !
                     for (int r = 0; r < 16; ++r) kv16[0][r] = (f16)a[r];
                 } else {
                     f16x8 k0, k1;
-                    if (ROPE) {
+                    if (PRE) {
                         k0 = __builtin_bit_cast(f16x8, reinterpret_cast<const uint4*>(s_krot + wave * 32 + 16 * h)[0]);
                         k1 = __builtin_bit_cast(f16x8, reinterpret_cast<const uint4*>(s_krot + wave * 32 + 16 * h)[1]);
                     } else {
@@ -1028,7 +1060,7 @@ int64_t fq_kv_decode_ws_bytes(int batch, int num_heads, int head_dim) {   // for
 int fq_launch_kv_decode(f16* o, const f16* q, void* kv_data, void* kv_param, const int* indptr, const int* indices, const int* last,
                         int num_layers, int layer_idx, int num_heads, int page_size, int head_dim, int batch, const f16* qt,
                         int transpose_out, hipStream_t stream, bool f16_cache, float* ws, int splits, int qgroup, const f16* k_new,
-                        const f16* v_new, const void* t_image, int src_heads, int copies, const f16* rope_cos, const f16* rope_sin) {
+                        const f16* v_new, const void* t_image, int src_heads, int copies, const f16* rope_cos, const f16* rope_sin, bool had, float had_scale) {
     // num_heads: QUERY heads (q, o); qgroup of them share one set of rows; the cache holds (num_heads / qgroup) * copies heads: copies = 1 and
     // qgroup = 1 the reference's layout read head by head, copies = 1 and qgroup = g a cache that holds the KV heads once, copies = qgroup = g the
     // reference's layout (g identical copies per KV head) read ONE copy per group
@@ -1039,7 +1071,10 @@ int fq_launch_kv_decode(f16* o, const f16* q, void* kv_data, void* kv_param, con
     // k_new: the step's own row is quantised and appended by this launch (KvNew): INT4 cache, head_dim 128, page_size % 16 == 0 only
     // rope_cos / rope_sin [batch, head_dim]: that launch rotates its queries and the new K row first (fq_kv_decode_append_rope_i4)
     if ((rope_cos != nullptr) != (rope_sin != nullptr) || (rope_cos != nullptr && k_new == nullptr)) return -1000;
-    KvNew nw = {k_new, v_new, reinterpret_cast<const uint4*>(t_image), src_heads, rope_cos, rope_sin};
+    // had: that launch applies the normalised Hadamard rotation (had_scale = 1 / sqrt(head_dim)) to its queries and the new K row instead (fq_kv_decode_append_had_i4):
+    // no query transform, no image, no tables
+    if (had && (k_new == nullptr || qt != nullptr || t_image != nullptr || rope_cos != nullptr)) return -1000;
+    KvNew nw = {k_new, v_new, reinterpret_cast<const uint4*>(t_image), src_heads, had ? had_scale : 0.0f, rope_cos, rope_sin};
     if (k_new != nullptr && (f16_cache || head_dim != 128 || page_size % 16 || v_new == nullptr || src_heads < 1 || (num_heads / qgroup * copies) % src_heads)) return -1000;
     const bool append = k_new != nullptr;
     // (round 6) a shared cache with 2 or 4 query heads per KV head at head_dim 128: ONE workgroup per (request, KV head) serves its query heads
@@ -1051,14 +1086,14 @@ int fq_launch_kv_decode(f16* o, const f16* q, void* kv_data, void* kv_param, con
 #define FQ_DEC5(HD_, NW_, UNI_, F16_, SP_, QG_, AP_)                                                                   \
     {                                                                                                                 \
         constexpr size_t ns_ = (size_t)(NW_ * (64 / (HD_ / 32))), nch_ = (size_t)NW_ * 64 / HD_;                      \
-        constexpr size_t lds = sizeof(float) * (ns_ * (HD_ + 1 + 2) + QG_ * HD_ + ns_ + NW_ + nch_ + nch_ * (HD_ + 1)) + (AP_ == 2 ? 512 : AP_ ? 256 : 0); \
+        constexpr size_t lds = sizeof(float) * (ns_ * (HD_ + 1 + 2) + QG_ * HD_ + ns_ + NW_ + nch_ + nch_ * (HD_ + 1)) + (AP_ >= 2 ? 512 : AP_ ? 256 : 0); \
         FQ_RAISE_LDS_CAP((fq_kv_decode_kernel<HD_, NW_, UNI_, F16_, SP_, QG_, AP_>), lds);                            \
         hipLaunchKernelGGL((fq_kv_decode_kernel<HD_, NW_, UNI_, F16_, SP_, QG_, AP_>), grid, dim3(NW_ * 64), lds, stream, o, q, p, qt, transpose_out, ws, qgroup, nw); \
     }
 #define FQ_DEC4(HD_, NW_, UNI_, F16_, SP_, QG_)                                                                        \
     {                                                                                                                 \
         if constexpr (HD_ == 128 && UNI_ && !F16_) {                                                                  \
-            if (append && rope_cos != nullptr) FQ_DEC5(HD_, NW_, UNI_, F16_, SP_, QG_, 2) else if (append) FQ_DEC5(HD_, NW_, UNI_, F16_, SP_, QG_, 1) else FQ_DEC5(HD_, NW_, UNI_, F16_, SP_, QG_, 0) \
+            if (append && had) FQ_DEC5(HD_, NW_, UNI_, F16_, SP_, QG_, 3) else if (append && rope_cos != nullptr) FQ_DEC5(HD_, NW_, UNI_, F16_, SP_, QG_, 2) else if (append) FQ_DEC5(HD_, NW_, UNI_, F16_, SP_, QG_, 1) else FQ_DEC5(HD_, NW_, UNI_, F16_, SP_, QG_, 0) \
         } else FQ_DEC5(HD_, NW_, UNI_, F16_, SP_, QG_, 0)                                                         \
     }
 #define FQ_DEC3(HD_, NW_, UNI_, F16_, SP_)                                                                             \

@@ -102,6 +102,10 @@ def n_q_is_cache_heads(kv_data, src_heads, group):
 # 66.5 -> 61.6 us at one request, 105 -> 99.5 at 16 (512 pairs), 162.6 -> 157.7 at 64 requests on the shared cache (512 pairs); level at 1024 and
 # 2048 pairs; 368 -> 373-379 at 4096 pairs (the prologue in front of every one of eight rounds of workgroups costs more than the launch it saves).
 FUSE_APPEND_MAX_PAIRS = 1024
+# trans="had" on the fused-append route: the decode launch rotates its queries and the step's new K row itself (ops.kv_decode_append(had=True),
+# fq_kv_decode_append_had_i4) instead of two ops.hadamard launches per layer and step in front of it — same pages, scales and outputs, bit for bit.
+# False: the two launches, as before (tests and A/B measurements; profiles/kv_had_fused.txt).
+HAD_IN_LAUNCH = True
 # rotate: up to this many (request, group of four query heads) PAIRS of the launch that serves four query heads per workgroup (groups of 4 / 8 from
 # 32 (request, KV head) pairs on) the decode launch also applies the rotary embedding; beyond, ONE ops.rope launch rotates the step's q and k in
 # front of it. Pairs, not workgroups: a split launch starts several workgroups per pair, but it splits only while the launch has at most ~256 of
@@ -111,6 +115,15 @@ FUSE_APPEND_MAX_PAIRS = 1024
 # requests (256 pairs: one workgroup per CU either way), 125.1 / 136.1 / 127.5 at 64 (512), 195.7 / 203.2 / 199.3 at 128 (1024). With this
 # routing (second table there) rotate costs 3.1 / 5.6 us over no rope at 64 / 128 requests, 1.4 / 0.8 us above the one-launch form called directly. Launches of one or two query heads per workgroup keep their occupancy with rope and are not bounded here.
 ROPE_FUSE_MAX_FOUR_HEAD_WGS = 256
+# trans="had": the same kind of bound for the Hadamard rotation inside the launch (HAD_IN_LAUNCH), for the same reason: with the rotation the four-head
+# kernel is not held to 128 VGPRs (130: three waves per SIMD; held, it spills). Measured on a Llama-3-8B layer's captured step at 2048 cached tokens, the
+# two ops.hadamard launches in front of the fused append / the rotation inside it (profiles/kv_had_fused.txt, third table; us, two rounds): 96.3, 97.0 /
+# 89.8, 91.1 at 24 requests (192 such workgroups), 102.5, 103.3 / 97.2, 97.5 at 32 (256), 127.5, 128.0 / 129.9, 129.8 at 40 (320), 127.7, 127.9 / 130.0,
+# 130.4 at 48, 128.8, 128.5 / 133.3, 133.0 at 64 (512), 164.0, 162.8 / 157.6, 157.2 at 96 (768: four-wave workgroups, where it wins again), 197.8, 197.8 /
+# 200.0, 198.7 at 128 (1024). The crossover lies between 256 and 320 workgroups; beyond the bound the step keeps its two launches (the win at 96 requests
+# is left where it is: one bound, not a table). Launched eagerly from Python the one-launch form is 10 - 45 us ahead at every size. Launches of one or
+# two query heads per workgroup keep their occupancy and are not bounded here (tools/bench_qattention.py: ahead at every size, same file).
+HAD_FUSE_MAX_FOUR_HEAD_WGS = 256
 # chunk extend: from this many tokens per request on, a step after the prompt (a follow-up prompt, a prompt fed in pieces) runs its attention on
 # ops.kv_chunk_extend (128 (token, head) rows per workgroup, every tile of the cache unpacked once for all of them) instead of ops.kv_batch_extend
 # (16 rows per workgroup). Measured on Llama-3-8B heads, INT4 pages, 2048 cached rows per request (profiles/kv_chunk_extend.txt; chunk / extend, us): the
@@ -135,7 +148,8 @@ class MultiLayerPagedKVCache4Bit:
       the scale tensor is kept and filled with (1, 0) like the reference's, the prefill gets the UN-transformed states back
       (:262-263 are assigned before the transform and only the INT4 branch re-assigns them, :280-281).
     * ``trans`` "matmul*" (the learned K transform, with its inverse-transpose on the query side), "had" (QuaRot: a normalised
-      Hadamard rotation of keys and queries over head_dim, :64-67, here the register FWHT) or anything else (none).
+      Hadamard rotation of keys and queries over head_dim, :64-67, here the register FWHT; a decode step on the fused-append route rotates
+      inside its one launch, ``HAD_IN_LAUNCH``) or anything else (none).
     * ``cache_kwargs["attention_mask"]`` [bsz, seq] of 0 / 1 (ragged prompts, :315-326,362-372): the prompt tokens whose mask
       is 1 are compacted request by request into the cache; request lengths are the mask's row sums from then on (the mask
       grows by one column per decode step). As in the reference, all requests must need the same number of pages
@@ -184,7 +198,7 @@ class MultiLayerPagedKVCache4Bit:
         self._needs_init = [True] * n_layers
         self.fuse_append = bool(fuse_append)
         self.read_one_copy = bool(read_one_copy)
-        self._pending = None    # a decode step's (k, v, transform, index tensors, layer) not yet appended: the closure's launch will (fuse_append)
+        self._pending = None    # a decode step's (k, v, transform, index tensors, layer) not yet appended — un-rotated where that launch also applies the Hadamard rotation (last field) —: the closure's launch will (fuse_append)
         self.length = 0
         self.serial = next(_SERIAL)   # deploy.graphed keys its captured graphs by this, never by id(): a new cache allocated where a dropped one lay is another cache
         self.generation = 0     # bumped when the page / index storage moves: graphs captured over the old pointers are stale (deploy.graphed)
@@ -364,9 +378,11 @@ class MultiLayerPagedKVCache4Bit:
         """Append the rows a decode step left to its closure's launch if that closure was never called (the two-launch form's first launch)."""
         pend, self._pending = self._pending, None
         if pend is not None:
-            k, v, tk16, args, layer_idx, group, rope, _ = pend
+            k, v, tk16, args, layer_idx, group, rope, _, had = pend
             if rope is not None:                 # (the closure's launch would have rotated the row itself)
                 k = ops.rope(None, k, *rope)[1]
+            if had:                              # (... and applied the Hadamard rotation: HAD_IN_LAUNCH)
+                k = ops.hadamard(k)
             ops.kv_quant_append(k, v, tk16, *args, layer_idx, group)
 
     def _step_indptr(self, b, added, device):
@@ -478,13 +494,16 @@ class MultiLayerPagedKVCache4Bit:
         if rope is not None and not rope_fused:
             key_states = ops.rope(None, key_states.to(torch.float16).contiguous(), *rope)[1]
         orig_k, orig_v = key_states, value_states
-        if had:                                                         # :265-266 matmul_had_cuda on the keys
+        # trans="had" on the fused-append route with fp16 keys and no mask: the closure's launch rotates the row (and its queries) itself
+        had_in_launch = (had and HAD_IN_LAUNCH and fuse_geometry and mask is None and key_states.dtype == torch.float16
+                         and four_head_wgs <= HAD_FUSE_MAX_FOUR_HEAD_WGS)
+        if had and not had_in_launch:                                   # :265-266 matmul_had_cuda on the keys
             key_states = ops.hadamard(key_states.to(torch.float16).contiguous())
         fused = fuse_geometry and key_states.dtype == torch.float16
         if fused:
             # the closure's launch quantises and appends these rows itself (ops.kv_decode_append)
             self._pending = (key_states.contiguous(), value_states.contiguous(), tk16, args, layer_idx, self.group_size,
-                             (rope[0].view(b, hd), rope[1].view(b, hd)) if rope_fused else None, rope_in_launch)
+                             (rope[0].view(b, hd), rope[1].view(b, hd)) if rope_fused else None, rope_in_launch, had_in_launch)
             keys_t = None
         elif not self.disable_quant and not ragged_init:
             # K transform + K / V quantisation + append: one launch (fq_kv_quant_append_i4); every request appends `added`
@@ -536,7 +555,7 @@ class MultiLayerPagedKVCache4Bit:
             mine = pend is not None and pend[3] is args and pend[4] == layer_idx      # this step's rows: appended by the decode launch itself
             if rope is not None and not (mine and pend[6] is not None):              # (rotate: ... which also rotates, or the launch of its own)
                 q2 = ops.rope(q2.contiguous(), None, rope[0].view(b, hd), rope[1].view(b, hd))[0]
-            if had:                                                         # :134-138: the query side of the rotation
+            if had and not (mine and pend[8]):                              # :134-138: the query side of the rotation (HAD_IN_LAUNCH: in the launch below)
                 q2 = ops.hadamard(q2.contiguous())
             elif tk_inv_t is not None:                                      # :139-140: ... of the learned K transform, in the launch
                 qt = self._as_f16(tk_inv_t)
@@ -547,7 +566,7 @@ class MultiLayerPagedKVCache4Bit:
                     q2, k_new = ops.rope(q2.contiguous(), k_new, *tabs)
                     tabs = None
                 return ops.kv_decode_append(q2.contiguous(), k_new, pend[1].view(b, heads, hd), pend[2], *args, layer_idx,
-                                            qt, transposed, seq_hint=length_now, read_one_copy=copies > 1, rope=tabs).unsqueeze(1)
+                                            qt, transposed, seq_hint=length_now, read_one_copy=copies > 1, rope=tabs, had=pend[8]).unsqueeze(1)
             self._flush_pending()
             return ops.kv_batch_decode(q2.contiguous(), *args, layer_idx, qt, transposed, seq_hint=length_now, kv_copies=copies).unsqueeze(1)
         return attend

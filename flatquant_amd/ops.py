@@ -2024,7 +2024,7 @@ def kv_transform_image(trans: torch.Tensor) -> torch.Tensor:
 def kv_decode_append(q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, trans: Optional[torch.Tensor], kv_data: torch.Tensor,
                      kv_param: torch.Tensor, kv_indptr: torch.Tensor, kv_indices: torch.Tensor, last_page_offset: torch.Tensor,
                      layer_idx: int, q_trans: Optional[torch.Tensor] = None, transpose_out: bool = False, seq_hint: int = 0,
-                     split: bool = True, read_one_copy: bool = False, rope=None) -> torch.Tensor:
+                     split: bool = True, read_one_copy: bool = False, rope=None, had: bool = False) -> torch.Tensor:
     """kv_quant_append(k_new, v_new, trans, ...) + kv_batch_decode(q, ...) of a decode step as ONE launch (fq_kv_decode_append_i4, round 6): the
     index tensors already count the new token (as for kv_quant_append), k_new / v_new [batch, kv_heads, head_dim] fp16 are its keys / values
     (the cache's heads are a multiple of kv_heads: the reference's replicated layout, or the shared one), q [batch, heads, head_dim]. The
@@ -2033,7 +2033,12 @@ def kv_decode_append(q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, 
     reads the first copy of every group (as kv_batch_decode(kv_copies=...)) and writes the new row to all of them.
     ``rope`` = (cos, sin), each [batch, head_dim] fp16 (round 8, fq_kv_decode_append_rope_i4): q and k_new are the UN-rotated projections and the
     launch applies the step's rotary embedding to them itself — the queries before ``q_trans``, the new K row before ``trans``, never V: cache
-    contents and output bit-identical to ``rope(q, k_new, cos, sin)`` followed by this call without the argument."""
+    contents and output bit-identical to ``rope(q, k_new, cos, sin)`` followed by this call without the argument.
+    ``had=True`` (fq_kv_decode_append_had_i4; the cache's default ``trans="had"``): q and k_new are the UN-rotated projections and the launch applies
+    the normalised Hadamard rotation over head_dim to them itself, never to V: cache contents and output bit-identical to
+    ``kv_decode_append(hadamard(q), hadamard(k_new), v_new, None, ...)``. It excludes ``trans``, ``q_trans`` and ``rope`` (ValueError)."""
+    if had and (trans is not None or q_trans is not None or rope is not None):
+        raise ValueError("kv_decode_append(had=True): the launch's own Hadamard rotation excludes trans, q_trans and rope")
     _chk(q, "q"), _chk(k_new, "k_new"), _chk(v_new, "v_new"), _chk(kv_data, "kv_data", torch.uint8), _chk(kv_param, "kv_param")
     n_layers, cache_heads, page_size, hd = _kv_geometry(kv_data)
     batch = _chk_kv_index(kv_indptr, kv_indices, last_page_offset)
@@ -2067,7 +2072,10 @@ def kv_decode_append(q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, 
                 _ptr(kv_data), _ptr(kv_param), _ptr(kv_indptr), _ptr(kv_indices), _ptr(last_page_offset),
                 n_layers, layer_idx, cache_heads, q_group, page_size, hd, batch, int(seq_hint), 1 if one else 0, _ptr(ws),
                 nbytes if ws is not None else 0, stream)
-        if cos is None:
+        if had:
+            had_scale = float(1.0 / torch.tensor(hd).sqrt())  # the fp32 value ops.hadamard passes for rows of head_dim
+            check(lib.fq_kv_decode_append_had_i4(*args[:2], *args[3:6], *args[7:], ctypes.c_float(had_scale)))
+        elif cos is None:
             check(lib.fq_kv_decode_append_i4(*args))
         else:
             check(lib.fq_kv_decode_append_rope_i4(*args, _ptr(cos), _ptr(sin)))

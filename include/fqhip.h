@@ -649,7 +649,8 @@ int fq_kv_batch_decode_gqa(int fp16_cache, void* o, const void* q, const void* q
  * appends the step's K / V row (fq_kv_quant_append_i4) and the returned closure attends over the cache including it (batch_decode_i4): two
  * dependent launches. fq_kv_decode_append_i4 is both: the lengths (kv_indptr / last_page_offset) already count the new token, k_new / v_new
  * [batch, src_heads, head_dim] fp16 are its keys / values, k_trans_image the K transform as fq_kv_transform_image_f16 wrote it
- * (fq_kv_transform_image_bytes(head_dim) bytes, once per layer; NULL: keys are not transformed — trans "had" / none). The workgroup that owns a
+ * (fq_kv_transform_image_bytes(head_dim) bytes, once per layer; NULL: THIS launch does not transform the keys — no transform at all, or one the caller
+ * has applied to k_new and q already; the Hadamard rotation of trans "had" inside the launch is fq_kv_decode_append_had_i4 below). The workgroup that owns a
  * request's last row quantises the new row with fq_kv_quant_append_i4's arithmetic (lac off, as the cache's own calls), uses it from LDS and
  * writes it to the cache: the cache contents and o are bit-identical to fq_kv_quant_append_i4 followed by fq_kv_batch_decode_gqa.
  * The cache holds num_kv_heads heads = src_heads x group (group <= 8: the reference's replicated layout has num_kv_heads = query heads and
@@ -680,6 +681,21 @@ int fq_kv_decode_append_rope_i4(void* o, const void* q, const void* q_trans, int
                                 const void* kv_indices, const void* last_page_offset, int num_layers, int layer_idx, int num_kv_heads, int q_group,
                                 int page_size, int head_dim, int batch_size, int seq_hint, int read_one_copy, void* workspace, int64_t workspace_bytes,
                                 void* stream, const void* cos, const void* sin);
+
+/* THE HADAMARD ROTATION OF THE CACHE'S DEFAULT CONFIGURATION INSIDE THE DECODE LAUNCH. MultiLayerPagedKVCache4Bit(trans="had") — the reference's default
+ * (deploy/transformers/kv_cache.py:134-138 rotates the queries, :265-266 the keys, matmul_had_cuda over head_dim; benchmarks/layer_benchmark.py:62-78 measures
+ * that configuration) — paid two fq_hadamard_f16 launches per layer and step in front of fq_kv_decode_append_i4. fq_kv_decode_append_had_i4 is that launch
+ * with the rotation inside: it takes fq_kv_decode_append_i4's arguments without q_trans / k_trans_image, plus had_scale, and multiplies every query row and
+ * the new K row by the normalised Hadamard matrix of order head_dim itself; V is never rotated. q and k_new are the UN-rotated projections.
+ * Arithmetic: fq_hadamard_f16(n = head_dim, K = 1, scale = had_scale) — fp16 up-cast to fp32, the seven butterfly stages in ascending stride order (each
+ * output one fp32 a + b or a - b), one fp32 product with had_scale, one rounding to fp16. had_scale is the caller's fp32 1 / sqrt(head_dim).
+ * CONTRACT: cache bytes, (scale, zero) pairs and o are BIT-IDENTICAL to fq_hadamard_f16 on q and on k_new followed by fq_kv_decode_append_i4(q_trans = NULL,
+ * k_trans_image = NULL). Same argument checks, same geometries (head_dim 128, page_size % 16 == 0, INT4 pages; FQ_EUNSUPPORTED otherwise).
+ * Not in this launch: the query rotation of the non-appending decode launches, the K rotation of fq_kv_quant_append_i4, head_dim 64, the extend launches. */
+int fq_kv_decode_append_had_i4(void* o, const void* q, int transpose_out, const void* k_new, const void* v_new, int src_heads, const void* kv_data,
+                               const void* kv_param, const void* kv_indptr, const void* kv_indices, const void* last_page_offset, int num_layers, int layer_idx,
+                               int num_kv_heads, int q_group, int page_size, int head_dim, int batch_size, int seq_hint, int read_one_copy, void* workspace,
+                               int64_t workspace_bytes, void* stream, float had_scale);
 
 /* The reference's replicated layout READ ONE COPY PER GROUP (round 6, third session). kv_cache.py:286-296 stores every KV head once per query head
  * of its group: `copies` consecutive cache heads with identical rows (fq_kv_quant_append_i4 / fq_kv_append_* with group_size = copies write them

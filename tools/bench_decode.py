@@ -22,9 +22,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--bsz", type=int, default=16)
     ap.add_argument("--cache", type=int, default=2048, help="cached tokens per request")
+    ap.add_argument("--kv-trans", choices=["matmul", "had", "none"], default="matmul", help="the cache's K transform: the learned matrix (default, as every table before it), "
+                    "\"had\" (the cache class's own default: a Hadamard rotation of keys and queries, inside the decode launch where HAD_IN_LAUNCH routes it) or none")
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--two-launches", action="store_true", help="round 5's launch structure: transform launch + projection launch per group (no fused prologue)")
     ap.add_argument("--share-kv", action="store_true", help="the cache holds the KV heads once (share_kv_heads=True: 1 / group of the memory and of the rows a step reads)")
+    ap.add_argument("--had-in-launch", choices=["auto", "on", "off"], default="auto", help="--kv-trans had: the rotation inside the decode launch as the cache routes it (auto), "
+                    "at every size (on: HAD_FUSE_MAX_FOUR_HEAD_WGS lifted) or never (off: two ops.hadamard launches per step, HAD_IN_LAUNCH = False)")
     ap.add_argument("--layers", type=int, default=1, help="L decoder layers with their OWN weights and cache layers in one step (the time printed is per layer). One "
                                                           "layer's INT4 weights are 109 MB and stay in the 256 MB Infinity Cache from one replay to the next; with L >= 4 "
                                                           "(436 MB; fp16: 1.7 GB) every replay streams them from HBM, as a 32-layer model's step does")
@@ -38,6 +42,10 @@ def main():
                          "torch (transformers' apply_rotary_pos_emb: ~ten element-wise launches), launch (ops.rope: one launch for q and k), fused "
                          "(cache_kwargs['rotate']: inside the append + attention launch). The fp16 baseline step gets the torch ops unless 'none'")
     a = ap.parse_args()
+    if a.had_in_launch != "auto":
+        from flatquant_amd.deploy.transformers import kv_cache as kvc
+        kvc.HAD_IN_LAUNCH = a.had_in_launch == "on"
+        kvc.HAD_FUSE_MAX_FOUR_HEAD_WGS = 1 << 30
     hidden, ffn, heads, kv_heads, hd = 4096, 14336, 32, 8, 128
     dev = torch.device("cuda")
     g = torch.Generator(device=dev).manual_seed(0)
@@ -75,7 +83,7 @@ def main():
     layers = [make_layer() for _ in range(L)]
     qkv_t, ug_t, o_t, down_t, q_l, k_l, v_l, o_l, up_l, gate_l, down_l = layers[0]
     tk = (torch.randn(hd, hd, generator=g, device=dev) / hd ** 0.5).half()
-    cache = dt.MultiLayerPagedKVCache4Bit(a.bsz, 2048, a.cache + 8, dev, L, heads, hd, trans="matmul", group_size=heads // kv_heads, share_kv_heads=a.share_kv, fuse_append=not a.no_fuse_append, read_one_copy=not a.no_one_copy)
+    cache = dt.MultiLayerPagedKVCache4Bit(a.bsz, 2048, a.cache + 8, dev, L, heads, hd, trans=a.kv_trans, group_size=heads // kv_heads, share_kv_heads=a.share_kv, fuse_append=not a.no_fuse_append, read_one_copy=not a.no_one_copy)
     kw = {"trans_matrix_k": tk, "trans_matrix_k_inv_t": tk}
     for li in range(L):
         cache.update(torch.randn(a.bsz, a.cache, kv_heads, hd, generator=g, device=dev).half(),
