@@ -14,6 +14,8 @@ int fq_launch_kron64_prepare(const void* left, const void* right, void* image, h
 int fq_launch_kron64_linear(const f16* x, const void* prep, int64_t M, float rms_eps, bool rms, int rt_flags, int n, const void* const* wimg,
                             const f16* const* scol, const f16* const* bias, const float* sig_max, const float* sig_min, const int* N,
                             f16* const* y, int n_cu, hipStream_t stream);
+int fq_launch_block_linear(const f16* x, const f16* P, int64_t M, int R, int C, float sig_max, float sig_min, int rt_flags, const void* wimg,
+                           const f16* scol, const f16* bias, int N, f16* y, int n_cu, hipStream_t stream);   // fq_block_linear.hip
 // The optional workspace of the 64 x 64 pair: the 16 KB fragment image fq_kron64_kernel reads, followed by the 16 KB image of the
 // workgroup-per-token kernel (the few output sets fq_kron64 has no instantiation for fall through to it).
 constexpr int64_t FQ_K64_IMAGE_BYTES = 16384, FQ_K64_WS_BYTES = 32768;
@@ -864,6 +866,27 @@ int fq_kron64_linear_multi_f16(const void* x, int rmsnorm, float rms_eps, const 
     rc = fq_launch_kron64_linear((const f16*)x, workspace, M, rms_eps, rmsnorm != 0, flags & (FQ_NO_CLAMP0 | FQ_ROUND_Y_F16), n, w_image,
                                  (const f16* const*)w_scale, (const f16* const*)bias, sig_max, sig_min, N, (f16* const*)y, cu_count(),
                                  (hipStream_t)stream);
+    if (rc == -1000) return fail(FQ_EUNSUPPORTED, "%s: shape not covered", what);
+    return check_launch(rc, what);
+}
+
+int fq_block_linear_f16(const void* x, const void* P, int64_t M, int R, int C, float sig_max, float sig_min, int flags, const void* w_image,
+                        const void* w_scale, const void* bias, int N, void* y, void* stream) {
+    const char* what = "fq_block_linear_f16";
+    // (every check sits in front of the first HIP call: cu_count() below)
+    if (!x || !P || !w_image || !w_scale || !y) return fail(FQ_EINVAL, "%s: x/P/w_image/w_scale/y is NULL", what);
+    FQ_NEED_ALIGN16(what, x, P, w_image);
+    if ((reinterpret_cast<uintptr_t>(w_scale) | reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(y)) & 1u)
+        return fail(FQ_EINVAL, "%s: w_scale / bias / y must be 2-byte aligned (fp16)", what);
+    if (M < 1 || N < 1 || R <= 0 || C <= 0) return fail(FQ_EINVAL, "%s: bad sizes M=%lld R=%d C=%d N=%d", what, (long long)M, R, C, N);
+    if (flags & ~FQ_NO_CLAMP0) return fail(FQ_EINVAL, "%s: unknown flag bits 0x%x (FQ_NO_CLAMP0 or 0)", what, flags);
+    if (!(sig_max > 0.0f) || !(sig_min > 0.0f)) return fail(FQ_EINVAL, "%s: sig_max/sig_min must be > 0", what);
+    if (R != 128 || C != 32)
+        return fail(FQ_EUNSUPPORTED, "%s: R=%d C=%d (the fused launch takes R = 128, C = 32; run fq_block_quant_f16 and the linear as two launches)", what, R, C);
+    if (M > 16) return fail(FQ_EUNSUPPORTED, "%s: M=%lld tokens (the fused launch takes 1..16; run the two launches)", what, (long long)M);
+    if (N & 31) return fail(FQ_EUNSUPPORTED, "%s: N=%d is not a multiple of 32", what, N);
+    const int rc = fq_launch_block_linear((const f16*)x, (const f16*)P, M, R, C, sig_max, sig_min, flags, w_image, (const f16*)w_scale,
+                                          (const f16*)bias, N, (f16*)y, cu_count(), (hipStream_t)stream);
     if (rc == -1000) return fail(FQ_EUNSUPPORTED, "%s: shape not covered", what);
     return check_launch(rc, what);
 }

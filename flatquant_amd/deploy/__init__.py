@@ -53,6 +53,55 @@ class LazyPackedQuantizedTensor(PackedQuantizedTensor):
         return torch.Size(self._shape)
 
 
+class LazyHeadPackedQuantizedTensor(PackedQuantizedTensor):
+    """What a fused o_proj pair hands out (deploy/fuse.py HeadGroup, decode-sized calls under capture): the Linear4bit behind the transform
+    runs it as its launch's prologue, so no packed bytes exist. The reference forward reshapes them between the two modules
+    (modeling_llama.py:143-144: ``x.quantized_x = x.quantized_x.contiguous().reshape(bsz, q_len, -1)``): ``.quantized_x`` answers with a
+    ``device="meta"`` uint8 tensor of the right shape, and assigning a meta tensor of the same numel only records the new shape — nothing is
+    launched, nothing materialised. ``.scales_x``, or assigning a real tensor, runs the transform's own launch once and turns this object
+    into a plain PackedQuantizedTensor (so does the group when a consumer other than its Linear4bit shows up)."""
+
+    def __init__(self, group, shape, device):
+        self._group, self._shape, self._device = group, tuple(shape), device
+
+    def realise(self):
+        r = self._group.materialise(self)
+        shape = self._shape
+        self.__class__ = PackedQuantizedTensor
+        self.__dict__.clear()
+        self.quantized_x, self.scales_x = r.quantized_x.reshape(shape), r.scales_x
+        return self
+
+    @property
+    def quantized_x(self):
+        return torch.empty(self._shape, dtype=torch.uint8, device="meta")
+
+    @quantized_x.setter
+    def quantized_x(self, v):
+        n = 1
+        for d in self._shape:
+            n *= d
+        if isinstance(v, torch.Tensor) and v.device.type == "meta" and v.dtype == torch.uint8 and v.numel() == n:
+            self._shape = tuple(v.shape)
+            return
+        self.realise().quantized_x = v      # (a caller that replaces the bytes owns them from then on)
+
+    @property
+    def scales_x(self):
+        return self.realise().scales_x
+
+    def size(self):
+        return torch.Size(self._shape)
+
+    @property
+    def device(self):
+        return self._device
+
+    @property
+    def dtype(self):
+        return torch.uint8
+
+
 def flatten_last_dim_and_return_shape(x: torch.Tensor):
     shape_excl_last = x.shape[:-1]
     return x.view(-1, x.shape[-1]), shape_excl_last

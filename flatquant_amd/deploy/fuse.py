@@ -30,7 +30,7 @@ import torch
 
 from .. import ops
 from .graphed import GraphedDecode
-from .nn.linear import Linear4bit, _fused_decode_problems, fused_transform_linear, linear4bit_multi
+from .nn.linear import Linear4bit, _fused_decode_problems, _fused_head_problem, fused_transform_linear, linear4bit_multi
 from .nn.online_trans import FusedSequential, OnlineTrans, fused_forward
 from .nn.quantization import Quantizer
 
@@ -168,12 +168,79 @@ class LinearGroup:
         return y
 
 
+class HeadGroup:
+    """The o_proj pair of one attention (``fuse(model, o_proj=True)``): ``o_proj_trans`` (a matmul OnlineTrans over the heads, not
+    decomposed) and the Linear4bit of ``o_proj = Sequential(Quantizer, Linear4bit)``. A decode-sized call of the transform under stream
+    capture (the rule of TransformGroup.get) whose shape the fused launch covers hands out a lazy packed tensor; the Linear4bit called
+    with it — through the reference's reshape of ``.quantized_x`` and the Quantizer, which passes packed inputs through — runs
+    fused_transform_linear: ONE launch, the packed bytes never exist. Anything else (eager or prefill-sized calls, another consumer, a
+    real tensor assigned to ``.quantized_x``) runs the modules' own forward."""
+
+    def __init__(self, trans, linear):
+        self.trans, self.linear = trans, linear
+        self._out = None          # the lazy tensor handed out last and not yet consumed
+        self._lazy_x = None       # its input
+        self._busy = False        # inside the members' own forward (materialise / fused_transform_linear's fall-back)
+        self.launches = 0         # transform launches of its own (a lazy result was materialised)
+        self.fused = 0            # launches that carried the transform as their prologue
+        self.lazy = 0
+
+    def drop(self):
+        self._out, self._lazy_x = None, None
+
+    def materialise(self, lazy):
+        """The real packed tensor behind ``lazy`` (somebody other than the group's Linear4bit asked for the bytes): the transform's own launch."""
+        if lazy is not self._out or self._lazy_x is None:
+            raise RuntimeError("a lazy PackedQuantizedTensor outlived its group's call")
+        x = self._lazy_x
+        self.drop()
+        self._busy = True
+        try:
+            real = self.trans(x)
+        finally:
+            self._busy = False
+        self.launches += 1
+        return real
+
+    def get(self, member, x):
+        if self._busy:
+            return None
+        if member is self.trans:
+            if not (isinstance(x, torch.Tensor) and x.dim() == 4 and x.is_cuda):
+                return None
+            if x.shape[0] * x.shape[1] > DECODE_ROWS or not torch.cuda.is_current_stream_capturing():
+                return None                                  # prefill-sized, or decode-sized and eager: the module's own forward
+            if _fused_head_problem(x, self.trans, self.linear) is None:
+                return None
+            from . import LazyHeadPackedQuantizedTensor
+            bsz, seq, hd, heads = x.shape
+            self._out = LazyHeadPackedQuantizedTensor(self, (bsz, seq, hd * heads // 2 // heads, heads), x.device)   # (kronecker_matmul's shape)
+            self._lazy_x = x
+            self.lazy += 1
+            return self._out
+        from . import LazyHeadPackedQuantizedTensor
+        if type(x) is not LazyHeadPackedQuantizedTensor:
+            return None
+        lx = self._lazy_x
+        if x is not self._out or lx is None or x._shape != (lx.shape[0], lx.shape[1], self.linear.in_features // 2):
+            x.realise()                                      # not this group's tensor, or not in the shape the reference hands over
+            return None
+        self.drop()
+        self._busy = True
+        try:
+            y = fused_transform_linear(lx, [self.trans], [self.linear])[0]      # ONE launch: transform + quantiser + projection
+        finally:
+            self._busy = False
+        self.fused += 1
+        return y
+
+
 def _is_trans(m):
     return isinstance(m, OnlineTrans) and m.trans == "matmul" and m.decompose
 
 
 def fuse(model: torch.nn.Module, down_proj: bool = True, linears: bool = True, static_outputs: bool = False,
-         fp6_image=None, fp6_image_budget_bytes=None, capture: bool = False) -> dict:
+         fp6_image=None, fp6_image_budget_bytes=None, capture: bool = False, o_proj: bool = False) -> dict:
     """Walk ``model`` (built by the reference's deploy/transformers/modeling_llama.py with ``import flatquant_amd.deploy as deploy``)
     and install the fused launches described in this module's docstring. Idempotent. ``static_outputs=True`` additionally sets the
     modules' opt-in static output plans (results rewritten by the next call of the same module — safe for the reference's forward,
@@ -183,8 +250,13 @@ def fuse(model: torch.nn.Module, down_proj: bool = True, linears: bool = True, s
     whether the layer keeps its FP6 operand image (+0.75 B/param, the prefill GEMM 1.6x faster) and the cap on what all images may hold
     together — the memory side of the deployment in the one call that configures it (INTEGRATION.md "Memory").
     ``capture=True`` (round 6): every decoder layer (a module with ``self_attn`` and ``mlp`` children, the reference's LlamaDecoderLayer
-    shape) serves its decode-sized calls from captured HIP graphs, transparently — deploy/graphed.py; reported as ``"graphed_layers"``."""
+    shape) serves its decode-sized calls from captured HIP graphs, transparently — deploy/graphed.py; reported as ``"graphed_layers"``.
+    ``o_proj=True`` (opt-in): every module with an ``o_proj_trans`` (a matmul OnlineTrans over the heads, ``decompose=False``) and an
+    ``o_proj = Sequential(Quantizer, Linear4bit)`` gets a ``HeadGroup``: decode-sized calls under capture run the head transform as the
+    prologue of o_proj's GEMM launch (fq_block_linear_f16); reported as ``"o_proj"``. A module whose pair has another form raises."""
     report = {"transform_groups": 0, "linear_groups": 0, "down_proj": 0}
+    if o_proj:
+        report["o_proj"] = 0
     if capture:
         report["graphed_layers"] = 0
         for mod in model.modules():
@@ -215,6 +287,15 @@ def fuse(model: torch.nn.Module, down_proj: bool = True, linears: bool = True, s
                 for l in ls:
                     l.__dict__["_group"] = lg
                 report["linear_groups"] += 1
+        ot, op = getattr(mod, "o_proj_trans", None), getattr(mod, "o_proj", None)
+        if o_proj and isinstance(ot, torch.nn.Module) and isinstance(op, torch.nn.Module):
+            if not (isinstance(ot, OnlineTrans) and ot.trans == "matmul" and not ot.decompose):
+                raise RuntimeError("fuse(o_proj=True): o_proj_trans must be OnlineTrans(heads, trans='matmul', decompose=False)")
+            if not (isinstance(op, torch.nn.Sequential) and len(op) == 2 and isinstance(op[0], Quantizer) and isinstance(op[1], Linear4bit)):
+                raise RuntimeError("fuse(o_proj=True): o_proj must be Sequential(Quantizer, Linear4bit)")
+            if "_group" not in ot.__dict__ and "_group" not in op[1].__dict__:
+                ot.__dict__["_group"] = op[1].__dict__["_group"] = HeadGroup(ot, op[1])
+                report["o_proj"] += 1
         dp = getattr(mod, "down_proj", None)
         if (down_proj and type(dp) is torch.nn.Sequential and len(dp) >= 2 and isinstance(dp[0], OnlineTrans)
                 and isinstance(dp[1], Quantizer)):

@@ -141,7 +141,8 @@ class Linear4bit(torch.nn.Module):
             y = grp.get(self, x)
             if y is not None:
                 return y
-        q, scales_x = x.quantized_x, x.scales_x
+        scales_x = x.scales_x      # (the scales first: a lazy o_proj tensor nobody fused becomes real on this read, its bytes with it)
+        q = x.quantized_x
         if self.static_outputs:
             st = self.__dict__.get("_plan_state")
             if st is not None:
@@ -304,16 +305,70 @@ def _fused_decode_problems(x, transforms, linears):
     return problems
 
 
+FUSED_HEAD_ROWS = 4            # fused_transform_linear, o_proj: up to this many tokens the head transform runs as the GEMM launch's prologue
+                               # (0: the route is off). Measured, profiles/head_linear_fused.txt, the two ops from captured graphs: 7.32 -> 6.36 us
+                               # at 1 token, 8.10 -> 6.93 at 2, 8.03 -> 7.19 at 3, 8.28 -> 7.54 at 4 (two-launch spread 0.1 - 0.3); from 5 tokens
+                               # on the fused launch loses (8.13 -> 8.26 at 5, 8.16 -> 8.65 at 8, 8.88 -> 12.25 at 16). The Llama-3-8B decode step
+                               # shows no gain beyond its own spread at any batch size (1 / 2 / 4 requests: 61.6 -> 62.4, 64.9 -> 64.4,
+                               # 69.7 -> 70.0 us, two-launch spread 0.5 - 1.8)
+
+
+def _is_head_trans(t):
+    return getattr(t, "trans", None) == "matmul" and not getattr(t, "decompose", True) and "right_matrix" in t._buffers
+
+
+def _fused_head_problem(x, t, m):
+    """The (w_image, w_scale, bias) of ops.block_linear when the fused o_proj launch covers ``m(t(x))``, else None."""
+    from ... import ops as _ops
+    if not (x.dim() == 4 and x.is_cuda and x.dtype == torch.float16 and _is_head_trans(t)):
+        return None
+    bsz, seq, R, C = x.shape
+    rows = bsz * seq
+    P = t._buffers["right_matrix"]
+    if not (1 <= rows <= FUSED_HEAD_ROWS and _ops.block_linear_supported(rows, R, C, m.out_features) and m.in_features == R * C
+            and tuple(P.shape) == (C, C) and P.dtype == torch.float16):
+        return None
+    dimg = m._decode_image()
+    if dimg is None:
+        return None
+    ws16, b16 = m._scales16()
+    return dimg, ws16, b16
+
+
+def _head_transform_linear(x, t, m):
+    """``m(t(x))`` for the o_proj pair (modeling_llama.py:141-148): one non-decomposed matmul OnlineTrans over the heads of
+    x [bsz, seq, head_dim, heads], the reference's reshape of the packed bytes to [bsz, seq, -1], one Linear4bit."""
+    from ... import ops as _ops
+    from ..._lib import FQ_NO_CLAMP0
+    if x.dim() != 4:
+        raise RuntimeError("fused_transform_linear: a non-decomposed transform takes x [bsz, seq, head_dim, heads]")
+    bsz, seq = x.shape[0], x.shape[1]
+    problem = _fused_head_problem(x, t, m)
+    if problem is not None:
+        sig = _ops.sigmoid_pair(t.clip_factor_a_max, t.clip_factor_a_min)          # (as functional.online_trans.kronecker_matmul)
+        y = _ops.block_linear(x.contiguous(), t._buffers["right_matrix"].contiguous(), sig, *problem, m.out_features, FQ_NO_CLAMP0)
+        if y is not None:
+            return y.view(bsz, seq, m.out_features)
+    p = t(x)
+    p.quantized_x = p.quantized_x.contiguous().reshape(bsz, seq, -1)
+    return m(p)
+
+
 def fused_transform_linear(x, transforms, linears, norm=None):
     """``[m(t(norm(x))) for t, m in zip(transforms, linears)]`` — the OnlineTrans modules of one attention / MLP (sharing their Kronecker
     pair, their own clip factors: fused_forward's contract) and the Linear4bit projections behind them — with THE TRANSFORM AS THE GEMM'S
     PROLOGUE where that pays (round 6): up to FUSED_DECODE_ROWS tokens of d = 4096 run as ONE launch (fq_kron64_linear_multi_f16: every
     workgroup transforms and quantises the tokens itself while its weights are in flight; the packed activations never reach memory);
-    anything else as fused_forward + linear4bit_multi. Bit-identical either way (tests/test_gpu_fused_decode.py)."""
+    anything else as fused_forward + linear4bit_multi. Bit-identical either way (tests/test_gpu_fused_decode.py).
+    ONE non-decomposed matmul transform (o_proj_trans: OnlineTrans(heads, trans="matmul", decompose=False)) with ONE Linear4bit and
+    x [bsz, seq, head_dim, heads]: up to FUSED_HEAD_ROWS tokens of a covered shape run fq_block_linear_f16, anything else the transform,
+    the reshape of its packed bytes to [bsz, seq, -1] and the module's own forward (tests/test_gpu_head_linear.py)."""
     from ... import ops as _ops
     from ..._lib import FQ_NO_CLAMP0, FQ_ROUND_Y_F16
     from ..functional.online_trans import deploy_kron_flags
     from .online_trans import fused_forward
+    if len(transforms) == 1 and len(linears) == 1 and norm is None and _is_head_trans(transforms[0]):
+        return [_head_transform_linear(x, transforms[0], linears[0])]
     problems = _fused_decode_problems(x, transforms, linears)
     if problems is not None:
         first = transforms[0]

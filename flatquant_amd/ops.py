@@ -1532,6 +1532,38 @@ def kron64_linear_multi(x: torch.Tensor, left: torch.Tensor, right: torch.Tensor
     return ys
 
 
+def block_linear_supported(M: int, R: int, C: int, N: int) -> bool:
+    """Does the fused o_proj launch (fq_block_linear_f16) cover M tokens of [R, C] blocks in front of an N-feature Linear4bit?
+    R = head_dim = 128 and C = heads = 32 (hidden size 4096), 1..16 tokens, N a multiple of 32."""
+    return R == 128 and C == 32 and 1 <= M <= FUSED_DECODE_MAX_ROWS and N >= 32 and N % 32 == 0
+
+
+def block_linear(x: torch.Tensor, P: torch.Tensor, sig: Sig, w_image: torch.Tensor, w_scale: torch.Tensor, bias: Optional[torch.Tensor],
+                 N: int, flags: int = FQ_NO_CLAMP0) -> Optional[torch.Tensor]:
+    """The head transform as the GEMM's prologue, decode regime (fq_block_linear_f16): x [..., R, C] @ P [C, C], the per-token INT4 quantiser
+    of the transposed block with the clip pair ``sig``, and the Linear4bit (w_image of int4_to_frag, w_scale [N], bias [N] or None) as ONE
+    launch -> fp16 [M, N], bit-identical to block_quant(x, P, [sig], FQ_OUT_PACKED | flags, transpose_out=True) followed by
+    int4_skinny_linear. None when the shape is not covered (block_linear_supported): the caller runs the two launches."""
+    if x.dim() < 2 or x.dtype != torch.float16:
+        return None
+    R, C = x.shape[-2], x.shape[-1]
+    M = x.numel() // (R * C) if R * C else 0
+    if not block_linear_supported(M, R, C, N):
+        return None
+    _chk(x, "x"), _chk(P, "P"), _chk(w_scale, "w_scale"), _chk(w_image, "w_image", torch.uint8)
+    if bias is not None:
+        _chk(bias, "bias")
+    if P.shape != (C, C):
+        raise ValueError("P must be [C, C] with C = x.shape[-1]")
+    if w_scale.numel() != N or (bias is not None and bias.numel() != N) or w_image.numel() != int(lib.fq_int4_frag_bytes(N, R * C)):
+        raise RuntimeError("block_linear: scale / bias / image sizes do not match N / K")
+    y = torch.empty((M, N), dtype=torch.float16, device=x.device)
+    with _on(x.device):
+        check(lib.fq_block_linear_f16(_ptr(x), _ptr(P), M, R, C, ctypes.c_float(sig[0]), ctypes.c_float(sig[1]), flags, _ptr(w_image),
+                                      _ptr(w_scale), _ptr(bias), N, _ptr(y), _stream(x)))
+    return y
+
+
 def int4_to_bf6(q: torch.Tensor, weights: bool = False) -> torch.Tensor:
     """Packed INT4 [rows, K/2] -> the BF6 operand image of the FP6-path GEMM (fq_int4_to_bf6). ``weights``: the image of
     a Linear4bit.weight (convert once per layer); else of packed activations. K % 64 == 0."""

@@ -409,6 +409,22 @@ int fq_kron64_linear_multi_f16(const void* x, int rmsnorm, float rms_eps, const 
                                const void* const* bias, const int* N, void* const* y, void* workspace, int64_t workspace_bytes, void* stream);
 
 /*
+ * THE HEAD TRANSFORM AS THE GEMM'S PROLOGUE, decode regime. ONE launch for what the reference runs as o_proj_trans -> quantizer -> o_proj
+ * on 1..16 tokens of hidden size 4096 (deploy/transformers/modeling_llama.py:141-148; deploy/kernels/block_matmul.py; deploy/nn/linear.py:40-54):
+ * x[t] [R, C] (R = head_dim, C = heads) . P [C, C], per-token INT4 quantisation with the clip pair (sig_max, sig_min) of the TRANSPOSED
+ * block [C][R], and the Linear4bit (w_image of fq_int4_to_frag(w [N, K/2], N, K = R C), w_scale [N] fp16, bias [N] fp16 or NULL) ->
+ * y [M, N] fp16. The quantised activations are never written to memory: every workgroup repeats the transform of the M tokens while its
+ * weights are in flight (profiles/head_linear_fused.txt).
+ * Bit-identical to fq_block_quant_f16(x, P, M, R, C, transpose_out = 1, one clip pair, FQ_OUT_PACKED | flags) followed by
+ * fq_int4_skinny_linear_f16(q, scale, w_image, w_scale, bias, M, N, R C, y).
+ *   flags: FQ_NO_CLAMP0 or 0; any other bit is FQ_EINVAL. NULL / misaligned pointers (x, P, w_image: 16 bytes; w_scale, bias, y: 2),
+ *   M < 1, N < 1, a clip factor <= 0: FQ_EINVAL.
+ *   FQ_EUNSUPPORTED (nothing is launched): anything but R = 128, C = 32, 1 <= M <= 16, N % 32 == 0 — run the two launches.
+ */
+int fq_block_linear_f16(const void* x, const void* P, int64_t M, int R, int C, float sig_max, float sig_min, int flags,
+                        const void* w_image, const void* w_scale, const void* bias, int N, void* y, void* stream);
+
+/*
  * The same GEMM / Linear4bit on the FP6 matrix path (v_mfma_scale_f32_32x32x64_f8f6f4, both operands BF6 = E3M2, unit
  * block scales): every integer in [-8, 7] is a BF6 value and the fp32 accumulator holds the exact integer sum
  * (K <= 2^18), so the results are bit-identical to fq_int4_gemm_i32 / fq_int4_linear_f16 — at ~1.4x the sustained

@@ -26,6 +26,8 @@ def main():
                     "\"had\" (the cache class's own default: a Hadamard rotation of keys and queries, inside the decode launch where HAD_IN_LAUNCH routes it) or none")
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--two-launches", action="store_true", help="round 5's launch structure: transform launch + projection launch per group (no fused prologue)")
+    ap.add_argument("--two-launch-o-proj", action="store_true", help="the o_proj head transform and its Linear4bit as two launches (fq_block_quant + the weight-streaming "
+                    "kernel) instead of fused_transform_linear's one where FUSED_HEAD_ROWS routes it (fq_block_linear_f16)")
     ap.add_argument("--share-kv", action="store_true", help="the cache holds the KV heads once (share_kv_heads=True: 1 / group of the memory and of the rows a step reads)")
     ap.add_argument("--had-in-launch", choices=["auto", "on", "off"], default="auto", help="--kv-trans had: the rotation inside the decode launch as the cache routes it (auto), "
                     "at every size (on: HAD_FUSE_MAX_FOUR_HEAD_WGS lifted) or never (off: two ops.hadamard launches per step, HAD_IN_LAUNCH = False)")
@@ -122,9 +124,12 @@ def main():
         q4, k4 = rope_qk(q.view(a.bsz, 1, heads, hd), k.view(a.bsz, 1, kv_heads, hd))
         attend = cache.update(k4, v.view(a.bsz, 1, kv_heads, hd), li, dict(kw_step))
         att_t = attend(q4, transposed=True)                # [bsz, 1, hd, heads]
-        po = o_t(att_t)
-        po.quantized_x = po.quantized_x.contiguous().reshape(a.bsz, 1, -1)
-        h2 = o_l(po)
+        if a.single or a.two_launches or a.two_launch_o_proj:
+            po = o_t(att_t)
+            po.quantized_x = po.quantized_x.contiguous().reshape(a.bsz, 1, -1)
+            h2 = o_l(po)
+        else:   # the head transform as o_proj's prologue up to FUSED_HEAD_ROWS tokens, the two launches otherwise
+            h2, = deploy.nn.fused_transform_linear(att_t, [o_t], [o_l])
         if a.single or a.two_launches:
             pu, pg = deploy.nn.fused_forward(h2, ug_t, norm=norm)
             if a.single:
@@ -154,9 +159,13 @@ def main():
                 q, k, v = deploy.nn.fused_transform_linear(h, qkv_t, [q_l, k_l, v_l], norm=norm)
                 q4, k4 = rope_qk(q.view(a.bsz, 1, heads, hd), k.view(a.bsz, 1, kv_heads, hd))
                 attend = cache.update(k4, v.view(a.bsz, 1, kv_heads, hd), li, dict(kw_step))
-                po = o_t(attend(q4, transposed=True))
-                po.quantized_x = po.quantized_x.contiguous().reshape(a.bsz, 1, -1)
-                yu, yg = deploy.nn.fused_transform_linear(o_l(po), ug_t, [up_l, gate_l], norm=norm)
+                if a.two_launch_o_proj:
+                    po = o_t(attend(q4, transposed=True))
+                    po.quantized_x = po.quantized_x.contiguous().reshape(a.bsz, 1, -1)
+                    h2 = o_l(po)
+                else:
+                    h2, = deploy.nn.fused_transform_linear(attend(q4, transposed=True), [o_t], [o_l])
+                yu, yg = deploy.nn.fused_transform_linear(h2, ug_t, [up_l, gate_l], norm=norm)
                 h = down_l(down_t(yg, up=yu))
             return h
 
