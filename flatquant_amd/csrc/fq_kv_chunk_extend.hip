@@ -24,6 +24,8 @@
 // (0 .. 15), score = s_k (q . n) - z_k sum_f q_f with sum_f q_f formed once per A row in fp32 (after q_trans). V sits in LDS as n - 8 and
 // o = sum_i a_i (n_i - 8) + sum_i p_i (8 s_i - z_i), a_i = fp16(256 p_i s_i) the one rounded quantity (the 256 keeps small weights out of the
 // fp16 subnormals, as in fq_kvextend.hip); the second sum is a scalar per A row carried beside the softmax denominator.
+// V rows with s >= 128 carry a power of two: they sit in LDS as (n - 8) 2^11 (|.| <= 16384) and their weight is fp16(256 p s 2^-11), exact both ways,
+// so a dominant row of any fp16 scale stays finite (p = 1 at s = 4368: 546). The commit step's packed add is a packed fma that carries it; the scale reaches the row's four threads by one DPP move.
 //
 // Causality and ends: tiles wholly above a wave's last visible row are skipped, only tiles that touch a diagonal or L_b pay for the mask.
 // Determinism: every sum of a token is formed tile by tile from row 0 in an order that depends on its absolute position, its head and the
@@ -66,15 +68,16 @@ __device__ __forceinline__ f16x4 cx_tr(const unsigned char* p) {
 __device__ __forceinline__ f16x8 cx_cat(f16x4 a, f16x4 b) { return f16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]}; }
 
 // the eight nibbles of a dword (feature 2 j in the low half of byte j) as eight fp16 values n + off16 - 16 in FEATURE order: kv_unpack8 leaves
-// 16 + n in the order 0 4 1 5 2 6 3 7, two byte permutes per pair put them back, one packed add takes the 16 away (exact)
-__device__ __forceinline__ uint4 cx_unpack(uint32_t w, uint32_t ebits, f16x2 off) {
+// 16 + n in the order 0 4 1 5 2 6 3 7, two byte permutes per pair put them back, one packed fma takes the 16 away (exact; mul: 1, or the power
+// of two of a V row with a large scale)
+__device__ __forceinline__ uint4 cx_unpack(uint32_t w, uint32_t ebits, f16x2 mul, f16x2 off) {
     uint32_t u[4];
     kv_unpack8(w, ebits, u);
     const uint32_t lo = 0x05040100u, hi = 0x07060302u;
     uint32_t n[4] = {__builtin_amdgcn_perm(u[1], u[0], lo), __builtin_amdgcn_perm(u[3], u[2], lo), __builtin_amdgcn_perm(u[1], u[0], hi),
                      __builtin_amdgcn_perm(u[3], u[2], hi)};
 #pragma unroll
-    for (int i = 0; i < 4; ++i) n[i] = __builtin_bit_cast(uint32_t, (f16x2)(__builtin_bit_cast(f16x2, n[i]) + off));
+    for (int i = 0; i < 4; ++i) n[i] = __builtin_bit_cast(uint32_t, __builtin_elementwise_fma(__builtin_bit_cast(f16x2, n[i]), mul, off));
     return make_uint4(n[0], n[1], n[2], n[3]);
 }
 
@@ -203,13 +206,17 @@ __global__ __launch_bounds__(CX_THREADS, 2) void fq_kv_chunk_extend_kernel(CxArg
             }
         } else {
             const uint32_t kw[4] = {kst[0].x, kst[0].y, kst[0].z, kst[0].w}, vw[4] = {vst[0].x, vst[0].y, vst[0].z, vst[0].w};
-            const f16x2 koff = {(f16)-16.0f, (f16)-16.0f}, voff = {(f16)-24.0f, (f16)-24.0f};   // K as n, V as n - 8
+            // K as n; V as n - 8, or (n - 8) 2^11 where the row's scale (held by the row's thread sc = 1) is >= 128
+            const uint32_t vpar = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)par, 0x55, 0xF, 0xF, false);   // quad_perm [1, 1, 1, 1]: one VALU move
+            const bool big = (vpar & 0x7FFFu) >= 0x5800u && (vpar & 0x7FFFu) < 0x7C00u;
+            const f16x2 one = {(f16)1.0f, (f16)1.0f}, koff = {(f16)-16.0f, (f16)-16.0f};
+            const f16x2 vmul = big ? f16x2{(f16)2048.0f, (f16)2048.0f} : one, voff = big ? f16x2{(f16)-49152.0f, (f16)-49152.0f} : f16x2{(f16)-24.0f, (f16)-24.0f};
 #pragma unroll
             for (int i = 0; i < 4; ++i) {                          // dword i: features 32 sc + 8 i ..+7 = chunk 4 sc + i
                 const int off = cl ^ (16 * i);
                 const uint4 z = make_uint4(0u, 0u, 0u, 0u);
-                *reinterpret_cast<uint4*>(st + off) = live ? cx_unpack(kw[i], ebits, koff) : z;
-                *reinterpret_cast<uint4*>(st + CX_TILE + off) = live ? cx_unpack(vw[i], ebits, voff) : z;
+                *reinterpret_cast<uint4*>(st + off) = live ? cx_unpack(kw[i], ebits, one, koff) : z;
+                *reinterpret_cast<uint4*>(st + CX_TILE + off) = live ? cx_unpack(vw[i], ebits, vmul, voff) : z;
             }
             if (sc < 2) {                                          // (a dead row: par = 0, all four values 0)
                 float* pp = reinterpret_cast<float*>(st + 2 * CX_TILE);
@@ -218,7 +225,7 @@ __global__ __launch_bounds__(CX_THREADS, 2) void fq_kv_chunk_extend_kernel(CxArg
                     pp[sr] = s * sm_scale;
                     pp[CX_KT + sr] = z * sm_scale;
                 } else {
-                    pp[2 * CX_KT + sr] = s * CX_PSCALE;
+                    pp[2 * CX_KT + sr] = s * (big ? CX_PSCALE * 0.00048828125f : CX_PSCALE);
                     pp[3 * CX_KT + sr] = 8.0f * s - z;
                 }
             }

@@ -136,6 +136,13 @@ __device__ __forceinline__ void kv_fma_half(float& acc, uint32_t pair, float s) 
 
 // sum_j q_j n_ij for the wave's RPW cached rows on the matrix pipe: A = the query in every row, B = the rows as columns. Lane
 // l = RPW g + i holds features 32 g .. 32 g + 31 of row i (one dword per K-step) and gets row i's sum over ALL features back.
+// Call it UNCONDITIONALLY and mask the result afterwards. `valid ? kv_qk_mfma(..) * s : -inf` evaluates the MFMA under the valid lanes' EXEC, and
+// a matrix instruction does not honour EXEC: the lanes of rows beyond the sequence got the raw, unscaled sum of whatever row they had loaded
+// as their score, and with it a reference maximum that the merge took for the request's. Every fp16-page launch of one query head did so in
+// its tail steps; with pages that are no multiple of the wave's rows the loaded row is entry 0 of the last page, and where its raw sum lay
+// ~120 above the largest scaled score every weight flushed to 0 and the launch returned zeros (tests/test_gpu_attn_closed_form.py, fp16 pages
+// at head_dim 64). Every call site (and every one of kv_qk_mfma4) now forms the sum first and selects afterwards; the compiler keeps the MFMA
+// in front of the select (no MFMA behind an EXEC-masked branch in the assembly of this file or of fq_kvextend.hip).
 template <int QL>
 __device__ __forceinline__ float kv_qk_mfma(const f16x8 (&qa)[4], const f16x8 (&kb)[4]) {
     if constexpr (QL == 4) {
@@ -500,6 +507,10 @@ __global__ __launch_bounds__(NW * 64, (KV_PVM_OCC4 && KV_PV_MFMA && QG == 4 && !
     // MFMAs accumulate O[head][feature] — 32 accumulator registers instead of 128. All rows of a wave feed one accumulator, so the softmax
     // reference m[g] is WAVE-uniform here (a bound KV_MARGIN above the largest score seen when it last moved — a wave reduction then, rare),
     // the denominators stay per lane. The zero-point sum uses the ROUNDED weights, so the 16-offset cancels exactly as before.
+    // LIMIT: fp16(256 p s_v) is finite while p s_v < 256 — a row that arrives in a later step of the wave within 8 log2 units above the row that
+    // set the reference has p up to 1 and overflows from there (tests/test_gpu_attn_closed_form.py: the marked riser cases). A wave-uniform slow
+    // path for rows with s_v >= 128 was built and measured: 128.7 -> 133.0 us per layer of the captured step at 64 requests, and scratch in the
+    // four-waves-per-SIMD variants (profiles/attn_closed_form.txt); not kept. The fp32 form below has no such product.
 #ifndef KV_PV_MFMA
 #define KV_PV_MFMA 1
 #endif
@@ -600,7 +611,8 @@ __global__ __launch_bounds__(NW * 64, (KV_PVM_OCC4 && KV_PV_MFMA && QG == 4 && !
 #pragma unroll
                 for (int g = 0; g < QG; ++g) x[g] = valid ? c4[g] * sm_scale : -INFINITY;
             } else {
-                x[0] = valid ? kv_qk_mfma<QL>(qa, kb) * sm_scale : -INFINITY;
+                const float dot = kv_qk_mfma<QL>(qa, kb);      // (every lane enabled: see kv_qk_mfma)
+                x[0] = valid ? dot * sm_scale : -INFINITY;
             }
         } else {
             const float ks = (float)__builtin_bit_cast(f16, (unsigned short)(r.kpar & 0xFFFF)), kz = (float)__builtin_bit_cast(f16, (unsigned short)(r.kpar >> 16));

@@ -19,6 +19,11 @@
 // maximum is uniform over the 16 lanes that hold the row's weights (a four-step reduction when it moves, rare). The causal mask only
 // touches rows >= L_b - T + 1: the steady-state loop stops there and stays free of conditions, the tail steps mask per A row.
 // With few workgroups the rows of a request are split over several of them (SPLIT: the decode's relaxed-atomic + vmcnt hand-over).
+// LIMIT (INT4 pages): a16 = fp16(256 p s_v) is finite while p s_v < 256. The reference sits 2^8 above the score that last moved it, so a
+// dominant row alone has p = 2^-8; a row that arrives in a later step of the same wave within 8 log2 units above the reference's row has p up
+// to 1 and overflows from p s_v >= 256 (tests/test_gpu_attn_closed_form.py: the marked riser cases). A wave-uniform slow path for rows with
+// s_v >= 128 (values times 2^11, weight times 2^-11) was built and measured: 442 -> 506 us at 8 x 2048 rows, T = 512
+// (profiles/attn_closed_form.txt); not kept.
 #include "fq_kv_common.hpp"
 #include <type_traits>
 

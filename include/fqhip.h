@@ -740,7 +740,11 @@ int fq_kv_batch_decode_copies(int fp16_cache, void* o, const void* q, const void
  *      q' = fp16(q . q_trans) inside the launch.
  *   head_dim 128 (64: FQ_EUNSUPPORTED); any page_size; q_len < 1 or bad head arithmetic: FQ_EINVAL.
  *   workspace: fq_kv_extend_workspace_bytes(batch_size, H, q_len, head_dim) bytes (0: never split) — the contract of fq_kv_batch_decode_split:
- *   16-byte aligned, zeroed once, used by one launch at a time and for ONE geometry; NULL: no split. seq_hint as there. */
+ *   16-byte aligned, zeroed once, used by one launch at a time and for ONE geometry; NULL: no split. seq_hint as there.
+ *   LIMIT (INT4 pages; the same in the four-head launch of fq_kv_batch_decode_gqa / _copies and fq_kv_decode_append*_i4): the weight of a V row
+ *   of scale s_v enters the matrix pipe as fp16(256 p s_v), p relative to a reference 2^8 above the score that last moved it: finite while
+ *   p s_v < 256. A dominant row alone weighs 2^-8 and passes at any scale; a row that arrives in a LATER step of the same wave 0 .. 8 log2
+ *   units above the one that set the reference has p up to 1 and returns Inf / NaN from p s_v >= 256. */
 int64_t fq_kv_extend_workspace_bytes(int batch_size, int num_q_heads, int q_len, int head_dim);
 int fq_kv_batch_extend(int fp16_cache, void* o, const void* q, const void* q_trans, int transpose_out, const void* kv_data,
                        const void* kv_param, const void* kv_indptr, const void* kv_indices, const void* last_page_offset, int num_layers,
@@ -755,7 +759,8 @@ int fq_kv_batch_extend(int fp16_cache, void* o, const void* q, const void* q_tra
  * launches are bit-identical, and a step fed as two consecutive launches (the first with index tensors that describe the shorter length)
  * equals the one launch bit for bit. Rows 0 .. L_b - 1 of a request are assumed finite; rows at or beyond L_b are never read.
  *   head_dim 128 (64 / 96: FQ_EUNSUPPORTED); q_group 1, 2, 4 or 8 (any other: FQ_EUNSUPPORTED); any page_size >= 1; q_len < 1, a bad layer
- *   index, copies > 8, copies not dividing q_group or num_cache_heads: FQ_EINVAL. o, q, kv_data, q_trans 16-byte aligned. */
+ *   index, copies > 8, copies not dividing q_group or num_cache_heads: FQ_EINVAL. o, q, kv_data, q_trans 16-byte aligned.
+ *   INT4 pages: V rows with a scale >= 128 carry a power of two through the matrix pipe (exact), so a dominant row of any fp16 scale is finite. */
 int fq_kv_chunk_extend(int fp16_cache, void* o, const void* q, const void* q_trans, int transpose_out, const void* kv_data, const void* kv_param,
                        const void* kv_indptr, const void* kv_indices, const void* last_page_offset, int num_layers, int layer_idx,
                        int num_cache_heads, int q_group, int copies, int q_len, int page_size, int head_dim, int batch_size, void* stream);
