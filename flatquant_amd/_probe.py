@@ -14,7 +14,9 @@ _vp, _i64, _i = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
 SYMBOLS = {
     "fq_probe_mfma_32x32x16_f16": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "fq_probe_stream_4096": (_i, [_vp, _i64, _vp, _vp, _i, _vp]),
+    "fq_probe_sfu_f32": (_i, [_i, _vp, _vp, _i64, _vp]),
 }
+SFU_OPS = {"rsq": 0, "exp2": 1, "rcp": 2}
 _lib = None
 
 
@@ -53,3 +55,14 @@ def probe_stream_4096(x: torch.Tensor, q: torch.Tensor, s: torch.Tensor, waves_p
         rc = lib().fq_probe_stream_4096(x.data_ptr(), rows, q.data_ptr(), s.data_ptr(), waves_per_simd, _stream(x))
     if rc != 0:
         raise RuntimeError(f"fq_probe_stream_4096 failed ({rc})")
+
+
+def probe_sfu(op: str, x: torch.Tensor) -> torch.Tensor:
+    """y = v_rsq_f32 / v_exp_f32 (2^x) / v_rcp_f32 of an fp32 tensor, elementwise (op: 'rsq', 'exp2', 'rcp')."""
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and op in SFU_OPS
+    y = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        rc = lib().fq_probe_sfu_f32(SFU_OPS[op], x.data_ptr(), y.data_ptr(), x.numel(), _stream(x))
+    if rc != 0:
+        raise RuntimeError(f"fq_probe_sfu_f32 failed ({rc})")
+    return y

@@ -46,9 +46,26 @@ __global__ __launch_bounds__(256) void fq_probe_stream_kernel(const u32x4* __res
     }
 }
 
+// y[i] = v_rsq_f32 / v_exp_f32 / v_rcp_f32 (x[i]) through the builtins the product kernels use (the RMSNorm reciprocal root, fq_silu8):
+// tests/test_gpu_prologue_ref.py measures their error against float64 before it derives anything from "1 ulp".
+__global__ __launch_bounds__(256) void fq_probe_sfu_kernel(int op, const float* __restrict__ x, float* __restrict__ y, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const float v = x[i];
+        y[i] = op == 0 ? __builtin_amdgcn_rsqf(v) : op == 1 ? __builtin_amdgcn_exp2f(v) : __builtin_amdgcn_rcpf(v);
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+int fq_probe_sfu_f32(int op, const void* x, void* y, int64_t n, void* stream) {
+    if (!x || !y || n <= 0 || op < 0 || op > 2) return -1;
+    int64_t blocks = (n + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(fq_probe_sfu_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, op, (const float*)x, (float*)y, n);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
 
 int fq_probe_mfma_32x32x16_f16(const void* A, const void* B, const void* C, void* D, void* stream) {
     if (!A || !B || !C || !D) return -1;

@@ -20,6 +20,10 @@ int fq_probe_mfma_32x32x16_f16(const void* A, const void* B, const void* C, void
  * waves_per_simd (1..8) sizes the persistent grid. */
 int fq_probe_stream_4096(const void* x, int64_t rows, void* q, void* s, int waves_per_simd, void* stream);
 
+/* Special-function probe: y[i] = v_rsq_f32 (op 0) / v_exp_f32 (op 1: 2^x) / v_rcp_f32 (op 2) of x[i], through the builtins the
+ * RMSNorm prologues and fq_silu8 use. x, y [n] fp32. The windows of tests/prologue_ref.py are derived from what this measures. */
+int fq_probe_sfu_f32(int op, const void* x, void* y, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

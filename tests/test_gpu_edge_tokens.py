@@ -12,7 +12,7 @@ constants, an all-zero scale group) at the odd positions, ordinary Gaussian rows
       takes an ordinary token straight after an edge token with the same LDS token buffer and reduction words. The same with NaN / Inf /
       overflowing rows (test names holding "nonfinite"): every OTHER row is bit-identical to the launch in which those rows are zero; the
       non-finite rows' own digits are pinned by no reference and not asserted. The launches whose prologue is not exact (RMSNorm, SiLU.mul,
-      the Hadamard rotations) are held under (c) only.
+      the Hadamard rotations) are held under (c) only HERE; tests/test_gpu_prologue_ref.py holds them to derived references.
 No tolerance, no flip rate, no skipped pair: where the library has no instantiation the refusal (FQ_EUNSUPPORTED / ValueError) is asserted."""
 import numpy as np
 import pytest
