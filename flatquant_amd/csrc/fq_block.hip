@@ -21,6 +21,7 @@
 // the GEMM has read the current one.
 #include "fq_common.hpp"
 #include "fq_dma.hpp"
+#include "fq_launch.hpp"
 
 namespace {
 
@@ -526,7 +527,7 @@ int launch_block_any_t(int flags, const T* x, const T* P, int64_t rows, int R, i
                              : launch_block_any<RT_, CT_, true, T>(flags, x, P, rows, C, out, n_cu, stream);
     FQ_BA(1, 1) FQ_BA(2, 1) FQ_BA(3, 1) FQ_BA(4, 1) FQ_BA(1, 2) FQ_BA(2, 2) FQ_BA(3, 2) FQ_BA(4, 2)
 #undef FQ_BA
-    return -1000;
+    return FQ_LAUNCH_NO_KERNEL;
 }
 
 template <int RT, int CT, bool NAT>
@@ -549,7 +550,7 @@ int launch_block(int flags, const f16* x, const f16* P, int64_t rows, const FqQu
 
 int fq_launch_block(int flags, const f16* x, const f16* P, int64_t rows, int R, int C, int transpose_out,
                     const FqQuantOut& out, int n_cu, hipStream_t stream) {
-    if ((R & 31) || R < 32 || R > 128 || (C & 1) || C < 2 || C > 64) return -1000;
+    if ((R & 31) || R < 32 || R > 128 || (C & 1) || C < 2 || C > 64) return FQ_LAUNCH_NO_KERNEL;
     if (flags & FQ_DT_BF16)
         return launch_block_any_t<bf16>(flags & ~FQ_DT_BF16, (const bf16*)x, (const bf16*)P, rows, R, C, transpose_out, out, n_cu, stream);
     if (C != 32 && C != 64) return launch_block_any_t<f16>(flags, x, P, rows, R, C, transpose_out, out, n_cu, stream);
@@ -560,5 +561,5 @@ int fq_launch_block(int flags, const f16* x, const f16* P, int64_t rows, int R, 
                              : launch_block<RT_, CT_, true>(flags, x, P, rows, out, n_cu, stream);
     FQ_B(1, 1) FQ_B(2, 1) FQ_B(3, 1) FQ_B(4, 1) FQ_B(1, 2) FQ_B(2, 2) FQ_B(3, 2) FQ_B(4, 2)
 #undef FQ_B
-    return -1000;
+    return FQ_LAUNCH_NO_KERNEL;
 }

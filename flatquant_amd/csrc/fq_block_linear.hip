@@ -21,6 +21,7 @@
 // As there, every VMEM operation is inline asm so that the compiler's own s_waitcnt bookkeeping never waits for the prefetched weights.
 #include "fq_common.hpp"
 #include "fq_gemm_common.hpp"
+#include "fq_launch.hpp"
 
 namespace {
 
@@ -270,10 +271,10 @@ __global__ __launch_bounds__(BL_THREADS) void fq_block_linear_kernel(const f16* 
 
 }  // namespace
 
-// The fused o_proj launch (fq_block_linear_f16): -1000 when the shape is not covered.
+// The fused o_proj launch (fq_block_linear_f16): FQ_LAUNCH_NO_KERNEL when the shape is not covered.
 int fq_launch_block_linear(const f16* x, const f16* P, int64_t M, int R, int C, float sig_max, float sig_min, int rt_flags, const void* wimg,
                            const f16* scol, const f16* bias, int N, f16* y, int n_cu, hipStream_t stream) {
-    if (R != BL_R || C != BL_C || M < 1 || M > BL_MAXM || N < 32 || (N & 31)) return -1000;
+    if (R != BL_R || C != BL_C || M < 1 || M > BL_MAXM || N < 32 || (N & 31)) return FQ_LAUNCH_NO_KERNEL;
     // workgroups: one per CU (or one per tile when there are fewer tiles), trimmed so that they walk the same number of tiles where the count
     // allows (fq_launch_kron64_linear)
     const int tiles = N >> 5;

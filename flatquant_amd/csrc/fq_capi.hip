@@ -4,108 +4,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 
 #include "fq_common.hpp"
-
-// launchers defined in the kernel translation units
-int fq_launch_kron64(int flags, const f16* x, const f16* left, const f16* right, const f16* diag,
-                     int64_t rows, const FqQuantOut& out, int n_cu, hipStream_t stream, const void* prep = nullptr);
-int fq_launch_kron64_prepare(const void* left, const void* right, void* image, hipStream_t stream);
-int fq_launch_kron64_linear(const f16* x, const void* prep, int64_t M, float rms_eps, bool rms, int rt_flags, int n, const void* const* wimg,
-                            const f16* const* scol, const f16* const* bias, const float* sig_max, const float* sig_min, const int* N,
-                            f16* const* y, int n_cu, hipStream_t stream);
-int fq_launch_block_linear(const f16* x, const f16* P, int64_t M, int R, int C, float sig_max, float sig_min, int rt_flags, const void* wimg,
-                           const f16* scol, const f16* bias, int N, f16* y, int n_cu, hipStream_t stream);   // fq_block_linear.hip
-// The optional workspace of the 64 x 64 pair: the 16 KB fragment image fq_kron64_kernel reads, followed by the 16 KB image of the
-// workgroup-per-token kernel (the few output sets fq_kron64 has no instantiation for fall through to it).
-constexpr int64_t FQ_K64_IMAGE_BYTES = 16384, FQ_K64_WS_BYTES = 32768;
-int fq_launch_kron_generic(int flags, const f16* x, const f16* left, const f16* right, const f16* diag,
-                           int64_t rows, int M, int N, const FqQuantOut& out, void* workspace,
-                           int64_t workspace_bytes, int n_cu, hipStream_t stream);
-int fq_launch_gemm_bf6_multi(int n, const uint8_t* const* xblob, const uint8_t* const* wblob, int64_t M, const int* Ns, int K, f16* const* y,
-                             const f16* const* srow, const f16* const* scol, const f16* const* bias, hipStream_t stream);   // fq_gemm_bf6.hip
-int fq_launch_fakequant_bits(int bf16_dtype, const void* x, void* y, int64_t rows, int cols, float sig_max, float sig_min, int bits, int flags,
-                             int n_cu, hipStream_t stream);   // fq_quant.hip
-int fq_launch_kron64_multi(int bf16_dtype, const void* jobs, int n_jobs, int bpj, const FqQuantOut& out, hipStream_t stream);
-int fq_launch_rowmm(int bf16_dtype, const void* x, const void* Tm, void* y, int64_t rows, int n, int n_cu, hipStream_t stream);
-int fq_launch_fwht_f32(const f16* x, float* y32, int64_t vecs, int P, float scale, int n_cu, hipStream_t stream);
-int fq_launch_had_mfma(const f16* x, int64_t rows, int n, int K, const f16* hadK, float scale, float sig_max, float sig_min,
-                       uint8_t* q_out, f16* scale_out, f16* y_out, int n_cu, hipStream_t stream, const f16* up = nullptr,
-                       int plain_quantizer = 0);
-int fq_launch_hadamard_quant(const f16* x, int64_t rows, int n, int K, const f16* hadK, float scale, float sig_max,
-                             float sig_min, uint8_t* q, f16* scale_out, int n_cu, hipStream_t stream);
-int fq_launch_gemm_i4(const uint8_t* X, const uint8_t* W, int64_t M, int N, int K, int32_t* c, f16* y, const f16* srow,
-                      const f16* scol, const f16* bias, hipStream_t stream);
-int fq_launch_rmsnorm(const f16* x, f16* y, int64_t rows, int cols, float eps, int n_cu, hipStream_t stream);
-int fq_launch_kv_quant(const f16* x, const f16* T, int64_t rows, int hd, float cmax, float cmin, bool lac, uint8_t* q,
-                       f16* param, f16* y, int n_cu, hipStream_t stream);
-int fq_launch_kv_dequant(const uint8_t* q, const f16* param, int64_t rows, int hd, bool lac, f16* y, int n_cu,
-                         hipStream_t stream);
-int fq_launch_kv_quant_append(const f16* k, const f16* v, const f16* T, int64_t tokens, int src_heads, int hd, const float* clip4,
-                              bool lac, void* kv_data, void* kv_param, const int* indptr, const int* indices, const int* last,
-                              int num_layers, int layer_idx, int num_heads, int page_size, int added, int group, int n_cu,
-                              hipStream_t stream);
-int64_t fq_i4_frag_bytes(int N, int K);
-int fq_launch_i4_to_frag(const uint8_t* W, int N, int K, void* img, int n_cu, hipStream_t stream);
-int fq_launch_gemm_i4_skinny_multi(int n, const uint8_t* const* X, const void* const* wimg, int64_t M, const int* N, int K, f16* const* y,
-                                   const f16* const* srow, const f16* const* scol, const f16* const* bias, hipStream_t stream);
-int64_t fq_gemm_i4_skinny_split_ws_bytes(int64_t M, int N, int K);
-int fq_launch_gemm_i4_skinny_split(const uint8_t* X, const void* wimg, int64_t M, int N, int K, f16* y, const f16* srow, const f16* scol,
-                                   const f16* bias, int* kws, hipStream_t stream);
-int fq_launch_gemm_i4_skinny(const uint8_t* X, const void* wimg, int64_t M, int N, int K, int32_t* c, f16* y, const f16* srow,
-                             const f16* scol, const f16* bias, hipStream_t stream);
-int64_t fq_bf6_blob_bytes(int64_t rows, int K);  // fq_gemm_bf6.hip (exported as is)
-int fq_launch_i4_to_bf6(const uint8_t* q, int64_t rows, int K, int perm, uint8_t* blob, int n_cu, hipStream_t stream);
-int fq_launch_i4_to_bf6_multi(int nsrc, const uint8_t* const* q, int64_t rows, int K, int perm, uint8_t* blob, int n_cu, hipStream_t stream);
-int fq_launch_gemm_bf6(const uint8_t* xblob, const uint8_t* wblob, int64_t M, int N, int K, int32_t* c, f16* y,
-                       const f16* srow, const f16* scol, const f16* bias, hipStream_t stream);
-int fq_launch_kv_append(void* kv_data, void* kv_param, const int* indptr, const int* indices, const int* last, const uint8_t* k,
-                        const uint8_t* v, const f16* kparam, const f16* vparam, const int* seqlen_indptr, int64_t total_tokens,
-                        int num_layers, int layer_idx, int num_heads, int page_size, int head_dim, int batch, int group, int n_cu,
-                        hipStream_t stream, bool f16_cache = false);
-int fq_launch_kv_decode(f16* o, const f16* q, void* kv_data, void* kv_param, const int* indptr, const int* indices, const int* last,
-                        int num_layers, int layer_idx, int num_heads, int page_size, int head_dim, int batch, const f16* qt,
-                        int transpose_out, hipStream_t stream, bool f16_cache = false, float* ws = nullptr, int splits = 1, int qgroup = 1,
-                        const f16* k_new = nullptr, const f16* v_new = nullptr, const void* t_image = nullptr, int src_heads = 1, int copies = 1,
-                        const f16* rope_cos = nullptr, const f16* rope_sin = nullptr, bool had = false, float had_scale = 0.0f);
-int fq_launch_rope(f16* q_out, f16* k_out, const f16* q, const f16* k, const f16* cos, const f16* sin, int64_t tokens, int q_heads, int k_heads,
-                   int head_dim, hipStream_t stream);
-int64_t fq_kv_timage_bytes(int hd);
-int fq_launch_kv_timage(const f16* T, int hd, void* img, hipStream_t stream);
-int fq_kv_decode_splits(int batch, int num_heads, int seq_hint);
-int fq_kv_decode_wg_heads(int batch, int num_q_heads, int q_group, int head_dim);
-int64_t fq_kv_decode_ws_bytes_gqa(int batch, int num_q_heads, int q_group, int head_dim);
-int64_t fq_kv_decode_ws_bytes(int batch, int num_heads, int head_dim);
-int64_t fq_kv_extend_ws_bytes(int batch, int num_q_heads, int q_len, int head_dim);   // fq_kvextend.hip
-int fq_launch_kv_extend(f16* o, const f16* q, const f16* qt, int transpose_out, void* kv_data, const void* kv_param, const int* indptr,
-                        const int* indices, const int* last, int num_layers, int layer_idx, int num_cache_heads, int q_group, int copies,
-                        int q_len, int page_size, int head_dim, int batch, int seq_hint, float* ws, int64_t ws_bytes, hipStream_t stream,
-                        bool f16_cache);
-int fq_launch_kv_chunk_extend(f16* o, const f16* q, const f16* qt, int transpose_out, const void* kv_data, const void* kv_param, const int* indptr,
-                              const int* indices, const int* last, int num_layers, int layer_idx, int num_cache_heads, int q_group, int copies,
-                              int q_len, int page_size, int head_dim, int batch, hipStream_t stream, bool f16_cache);   // fq_kv_chunk_extend.hip
-int fq_launch_prefill_attn(f16* o, const f16* q, const f16* qt, const f16* k, const f16* v, const int* seq_start, const int* seq_len, int batch,
-                           int seq, int q_heads, int kv_heads, hipStream_t stream);   // fq_prefill_attn.hip
-int fq_launch_silu_mul(const f16* gate, const f16* up, f16* y, int64_t n, int n_cu, hipStream_t stream);
-int fq_launch_silu_hadamard_quant(const f16* gate, const f16* up, int64_t rows, int n, int K, const f16* hadK, float scale,
-                                  float sig_max, float sig_min, uint8_t* q, f16* scale_out, int n_cu, hipStream_t stream);
-int64_t fq_kron_generic_workspace_bytes(int M, int N);
-int fq_launch_kron_prepare(const f16* left, const f16* right, int M, int N, void* workspace, hipStream_t stream, int groups = 1);
-int fq_launch_kron_grouped_mats(int flags, const void* x, const void* left, const void* right, int64_t rows, int M, int N,
-                                const FqQuantOut& out, int n_groups, void* workspace, int64_t workspace_bytes, int n_cu,
-                                hipStream_t stream);
-int fq_launch_block(int flags, const f16* x, const f16* P, int64_t rows, int R, int C, int transpose_out,
-                    const FqQuantOut& out, int n_cu, hipStream_t stream);
-int fq_launch_hadamard(const f16* x, f16* y, int64_t rows, int n, int K, const f16* hadK, float scale,
-                       int n_cu, hipStream_t stream);
-int fq_launch_rowquant(int flags, const f16* x, int64_t rows, int cols, const FqQuantOut& out, int n_cu,
-                       hipStream_t stream);
-int fq_launch_sym_quant(const f16* x, const f16* scale, int64_t rows, int cols, uint8_t* q, int n_cu,
-                        hipStream_t stream);
-int fq_launch_sym_dequant(const int32_t* q, const f16* srow, const f16* scol, int64_t rows, int cols,
-                          f16* x, int n_cu, hipStream_t stream);
-int fq_launch_kron64_trace(const f16* x, const f16* left, const f16* right, int64_t rows, const FqQuantOut& out,
-                           unsigned long long* trace, int n_cu, hipStream_t stream);
+#include "fq_launch.hpp"
 
 namespace {
 
@@ -144,7 +46,7 @@ int cu_count() {
 }
 
 int check_launch(int rc, const char* what) {
-    if (rc == -1000) return fail(FQ_EUNSUPPORTED, "%s: flag combination / shape has no compiled kernel", what);
+    if (rc == FQ_LAUNCH_NO_KERNEL) return fail(FQ_EUNSUPPORTED, "%s: flag combination / shape has no compiled kernel", what);
     if (rc != 0) return fail(FQ_ELAUNCH, "%s: HIP launch failed: %s", what, hipGetErrorString((hipError_t)rc));
     return FQ_OK;
 }
@@ -222,7 +124,7 @@ static int kron_dispatch(const char* what, const FqQuantOut& o, int flags, const
         }
         rc = fq_launch_kron64(flags & ~FQ_WS_PREPARED, (const f16*)x, (const f16*)left, (const f16*)right, (const f16*)diag,
                               rows, o, n_cu, (hipStream_t)stream, prep);
-        if (rc != -1000) return check_launch(rc, what);
+        if (rc != FQ_LAUNCH_NO_KERNEL) return check_launch(rc, what);
         if (dt) return fail(FQ_EUNSUPPORTED, "%s: output set 0x%x has no bf16 kernel at 64 x 64", what, flags & ~dt);
         if ((o.rt_flags & FQ_GROUP128) && !(flags & FQ_ROUND_Y_F16))
             return fail(FQ_EUNSUPPORTED, "%s: FQ_GROUP128 at 64 x 64 needs the packed-only output set or FQ_ROUND_Y_F16", what);
@@ -235,13 +137,13 @@ static int kron_dispatch(const char* what, const FqQuantOut& o, int flags, const
     }
     rc = fq_launch_kron_generic(flags, (const f16*)x, (const f16*)left, (const f16*)right, (const f16*)diag,
                                 rows, M, N, o, workspace, workspace_bytes, n_cu, (hipStream_t)stream);
-    if (rc == -1001)
+    if (rc == FQ_LAUNCH_NEED_WS)
         return fail(FQ_EINVAL, "%s: workspace of %lld bytes required for M=%d N=%d (got %lld)", what,
                     (long long)fq_kron_generic_workspace_bytes(M, N), M, N, (long long)(workspace ? workspace_bytes : 0));
-    if (rc == -1000 && special)
+    if (rc == FQ_LAUNCH_NO_KERNEL && special)
         return fail(FQ_EUNSUPPORTED, "%s: grouped / FQ_GROUP128 launches need a fused MFMA kernel; factors (%d, %d) with "
                     "flags 0x%x have none", what, M, N, flags);
-    if (rc == -1000)
+    if (rc == FQ_LAUNCH_NO_KERNEL)
         return fail(FQ_EUNSUPPORTED, "%s: no kernel for factors (%d, %d) with flags 0x%x: M, N <= 256, N even, M*N <= 32768", what, M, N, flags);
     return check_launch(rc, what);
 }
@@ -352,10 +254,10 @@ static int kron_quant_grouped_mats_impl(const char* what, int dt, const void* x,
     o.n_groups = n_groups;
     rc = fq_launch_kron_grouped_mats(flags | dt, x, left_g, right_g, rows, M, N, o, n_groups, workspace, workspace_bytes, cu_count(),
                                      (hipStream_t)stream);
-    if (rc == -1001)
+    if (rc == FQ_LAUNCH_NEED_WS)
         return fail(FQ_EINVAL, "%s: workspace of %lld bytes required for %d groups of M=%d N=%d (got %lld)", what,
                     (long long)(fq_kron_generic_workspace_bytes(M, N) * n_groups), n_groups, M, N, (long long)(workspace ? workspace_bytes : 0));
-    if (rc == -1000) return fail(FQ_EUNSUPPORTED, "%s: no workgroup-per-token kernel for factors (%d, %d)", what, M, N);
+    if (rc == FQ_LAUNCH_NO_KERNEL) return fail(FQ_EUNSUPPORTED, "%s: no workgroup-per-token kernel for factors (%d, %d)", what, M, N);
     return check_launch(rc, what);
 }
 
@@ -397,10 +299,10 @@ int fq_rmsnorm_kron_quant_ws_f16(const void* x, float eps, const void* left, con
     o.rms_eps = eps;
     rc = fq_launch_kron_generic(flags | FQ_IN_RMSNORM, (const f16*)x, (const f16*)left, (const f16*)right, nullptr, rows, M, N, o,
                                 workspace, workspace_bytes, cu_count(), (hipStream_t)stream);
-    if (rc == -1001)
+    if (rc == FQ_LAUNCH_NEED_WS)
         return fail(FQ_EINVAL, "%s: workspace of %lld bytes required for M=%d N=%d (got %lld)", what,
                     (long long)fq_kron_generic_workspace_bytes(M, N), M, N, (long long)(workspace ? workspace_bytes : 0));
-    if (rc == -1000)
+    if (rc == FQ_LAUNCH_NO_KERNEL)
         return fail(FQ_EUNSUPPORTED, "%s: the RMSNorm is fused for 64 x 64 and the wave-per-token pairs (M <= 64, N in {64, 80, 112, 128}); "
                     "run fq_rmsnorm_f16 first for (%d, %d)", what, M, N);
     return check_launch(rc, what);
@@ -423,7 +325,7 @@ int fq_rmsnorm_kron_quant_f16(const void* x, float eps, const void* left, const 
     o.rms_eps = eps;
     rc = fq_launch_kron64(flags | FQ_IN_RMSNORM, (const f16*)x, (const f16*)left, (const f16*)right, nullptr, rows, o,
                           cu_count(), (hipStream_t)stream);
-    if (rc == -1000) return fail(FQ_EUNSUPPORTED, "fq_rmsnorm_kron_quant_f16: output set 0x%x has no fused kernel", flags);
+    if (rc == FQ_LAUNCH_NO_KERNEL) return fail(FQ_EUNSUPPORTED, "fq_rmsnorm_kron_quant_f16: output set 0x%x has no fused kernel", flags);
     return check_launch(rc, "fq_rmsnorm_kron_quant_f16");
 }
 
@@ -441,10 +343,10 @@ int fq_silu_mul_kron_quant_f16(const void* gate, const void* up, const void* lef
     o.in2 = (const f16*)up;
     rc = fq_launch_kron_generic(flags | FQ_IN_SILU_MUL, (const f16*)gate, (const f16*)left, (const f16*)right, nullptr,
                                 rows, M, N, o, workspace, workspace_bytes, cu_count(), (hipStream_t)stream);
-    if (rc == -1001)
+    if (rc == FQ_LAUNCH_NEED_WS)
         return fail(FQ_EINVAL, "fq_silu_mul_kron_quant_f16: workspace of %lld bytes required for M=%d N=%d (got %lld)",
                     (long long)fq_kron_generic_workspace_bytes(M, N), M, N, (long long)(workspace ? workspace_bytes : 0));
-    if (rc == -1000)
+    if (rc == FQ_LAUNCH_NO_KERNEL)
         return fail(FQ_EUNSUPPORTED, "fq_silu_mul_kron_quant_f16: no fused kernel for M=%d N=%d (use fq_silu_mul_f16 + fq_kron_quant_f16)", M, N);
     return check_launch(rc, "fq_silu_mul_kron_quant_f16");
 }
@@ -474,10 +376,10 @@ int fq_kron_quant_ex_f16(const void* x, const void* up, const void* left, const 
     // M > 64, e.g. a Hadamard rotation of n = K * P as the Kronecker product (hadK x H_{P/N}) (x) H_N)
     rc = fq_launch_kron_generic(flags | (up ? FQ_IN_SILU_MUL : 0) | FQ_NO_WAVE_KERNEL, (const f16*)x, (const f16*)left, (const f16*)right,
                                 nullptr, rows, M, N, o, workspace, workspace_bytes, cu_count(), (hipStream_t)stream);
-    if (rc == -1001)
+    if (rc == FQ_LAUNCH_NEED_WS)
         return fail(FQ_EINVAL, "%s: workspace of %lld bytes required for M=%d N=%d (got %lld)", what,
                     (long long)fq_kron_generic_workspace_bytes(M, N), M, N, (long long)(workspace ? workspace_bytes : 0));
-    if (rc == -1000) return fail(FQ_EUNSUPPORTED, "%s: no kernel for M=%d N=%d with flags 0x%x", what, M, N, flags);
+    if (rc == FQ_LAUNCH_NO_KERNEL) return fail(FQ_EUNSUPPORTED, "%s: no kernel for M=%d N=%d with flags 0x%x", what, M, N, flags);
     return check_launch(rc, what);
 }
 
@@ -487,7 +389,7 @@ int fq_silu_mul_f16(const void* gate, const void* up, void* y, int64_t n, void* 
     if (n == 0) return FQ_OK;
     if (!gate || !up || !y) return fail(FQ_EINVAL, "fq_silu_mul_f16: NULL pointer");
     const int rc = fq_launch_silu_mul((const f16*)gate, (const f16*)up, (f16*)y, n, cu_count(), (hipStream_t)stream);
-    if (rc == -1000) return fail(FQ_EUNSUPPORTED, "fq_silu_mul_f16: n=%lld must be a multiple of 8", (long long)n);
+    if (rc == FQ_LAUNCH_NO_KERNEL) return fail(FQ_EUNSUPPORTED, "fq_silu_mul_f16: n=%lld must be a multiple of 8", (long long)n);
     return check_launch(rc, "fq_silu_mul_f16");
 }
 
@@ -504,7 +406,7 @@ int fq_silu_mul_hadamard_quant_f16(const void* gate, const void* up, int64_t row
     const int rc = fq_launch_silu_hadamard_quant((const f16*)gate, (const f16*)up, rows, n, K, (const f16*)hadK, scale,
                                                  sig_max, sig_min, (uint8_t*)q_out, (f16*)scale_out, cu_count(),
                                                  (hipStream_t)stream);
-    if (rc == -1000)
+    if (rc == FQ_LAUNCH_NO_KERNEL)
         return fail(FQ_EUNSUPPORTED, "fq_silu_mul_hadamard_quant_f16: no fused kernel for n=%d K=%d", n, K);
     return check_launch(rc, "fq_silu_mul_hadamard_quant_f16");
 }
@@ -515,7 +417,7 @@ int fq_rmsnorm_f16(const void* x, void* y, int64_t rows, int cols, float eps, vo
     if (rows < 0 || cols <= 0 || !(eps >= 0.0f)) return fail(FQ_EINVAL, "fq_rmsnorm_f16: bad arguments");
     if (rows == 0) return FQ_OK;
     const int rc = fq_launch_rmsnorm((const f16*)x, (f16*)y, rows, cols, eps, cu_count(), (hipStream_t)stream);
-    if (rc == -1000) return fail(FQ_EUNSUPPORTED, "fq_rmsnorm_f16: cols=%d must be a multiple of 8 and <= 16384", cols);
+    if (rc == FQ_LAUNCH_NO_KERNEL) return fail(FQ_EUNSUPPORTED, "fq_rmsnorm_f16: cols=%d must be a multiple of 8 and <= 16384", cols);
     return check_launch(rc, "fq_rmsnorm_f16");
 }
 
@@ -748,7 +650,7 @@ int fq_int4_gemm_i32(const void* x, const void* w, int64_t M, int N, int K, void
     if (M == 0) return FQ_OK;
     const int rc = fq_launch_gemm_i4((const uint8_t*)x, (const uint8_t*)w, M, N, K, (int32_t*)c, nullptr, nullptr, nullptr,
                                      nullptr, (hipStream_t)stream);
-    if (rc == -1000) return fail(FQ_EUNSUPPORTED, "fq_int4_gemm_i32: shape M=%lld N=%d K=%d not supported (K < 2^25)", (long long)M, N, K);
+    if (rc == FQ_LAUNCH_NO_KERNEL) return fail(FQ_EUNSUPPORTED, "fq_int4_gemm_i32: shape M=%lld N=%d K=%d not supported (K < 2^25)", (long long)M, N, K);
     return check_launch(rc, "fq_int4_gemm_i32");
 }
 
@@ -761,7 +663,7 @@ int fq_int4_linear_f16(const void* x, const void* x_scale, const void* w, const 
     if (M == 0) return FQ_OK;
     const int rc = fq_launch_gemm_i4((const uint8_t*)x, (const uint8_t*)w, M, N, K, nullptr, (f16*)y, (const f16*)x_scale,
                                      (const f16*)w_scale, (const f16*)bias, (hipStream_t)stream);
-    if (rc == -1000) return fail(FQ_EUNSUPPORTED, "fq_int4_linear_f16: shape M=%lld N=%d K=%d not supported (K < 2^25)", (long long)M, N, K);
+    if (rc == FQ_LAUNCH_NO_KERNEL) return fail(FQ_EUNSUPPORTED, "fq_int4_linear_f16: shape M=%lld N=%d K=%d not supported (K < 2^25)", (long long)M, N, K);
     return check_launch(rc, "fq_int4_linear_f16");
 }
 
@@ -780,7 +682,7 @@ int fq_int4_skinny_gemm_i32(const void* x, const void* w_image, int64_t M, int N
     if (!x || !w_image || !c) return fail(FQ_EINVAL, "fq_int4_skinny_gemm_i32: NULL pointer");
     const int rc = fq_launch_gemm_i4_skinny((const uint8_t*)x, w_image, M, N, K, (int32_t*)c, nullptr, nullptr, nullptr, nullptr,
                                             (hipStream_t)stream);
-    if (rc == -1000) return fail(FQ_EUNSUPPORTED, "fq_int4_skinny_gemm_i32: M=%lld K=%d (M <= 128, K %% 64 == 0, K < 131072)", (long long)M, K);
+    if (rc == FQ_LAUNCH_NO_KERNEL) return fail(FQ_EUNSUPPORTED, "fq_int4_skinny_gemm_i32: M=%lld K=%d (M <= 128, K %% 64 == 0, K < 131072)", (long long)M, K);
     return check_launch(rc, "fq_int4_skinny_gemm_i32");
 }
 
@@ -791,7 +693,7 @@ int fq_int4_skinny_linear_f16(const void* x, const void* x_scale, const void* w_
     if (!x || !w_image || !y || !x_scale || !w_scale) return fail(FQ_EINVAL, "fq_int4_skinny_linear_f16: NULL pointer");
     const int rc = fq_launch_gemm_i4_skinny((const uint8_t*)x, w_image, M, N, K, nullptr, (f16*)y, (const f16*)x_scale,
                                             (const f16*)w_scale, (const f16*)bias, (hipStream_t)stream);
-    if (rc == -1000) return fail(FQ_EUNSUPPORTED, "fq_int4_skinny_linear_f16: M=%lld K=%d (M <= 128, K %% 64 == 0, K < 131072)", (long long)M, K);
+    if (rc == FQ_LAUNCH_NO_KERNEL) return fail(FQ_EUNSUPPORTED, "fq_int4_skinny_linear_f16: M=%lld K=%d (M <= 128, K %% 64 == 0, K < 131072)", (long long)M, K);
     return check_launch(rc, "fq_int4_skinny_linear_f16");
 }
 
@@ -812,7 +714,7 @@ int fq_int4_skinny_linear_split_f16(const void* x, const void* x_scale, const vo
         return fail(FQ_EINVAL, "%s: workspace of %lld bytes, fq_int4_skinny_split_workspace_bytes says %lld", what, (long long)workspace_bytes, (long long)need);
     const int rc = fq_launch_gemm_i4_skinny_split((const uint8_t*)x, w_image, M, N, K, (f16*)y, (const f16*)x_scale, (const f16*)w_scale, (const f16*)bias,
                                                   need > 0 ? (int*)workspace : nullptr, (hipStream_t)stream);
-    if (rc == -1000) return fail(FQ_EUNSUPPORTED, "%s: M=%lld K=%d (M <= 128, K %% 64 == 0, K < 131072)", what, (long long)M, K);
+    if (rc == FQ_LAUNCH_NO_KERNEL) return fail(FQ_EUNSUPPORTED, "%s: M=%lld K=%d (M <= 128, K %% 64 == 0, K < 131072)", what, (long long)M, K);
     return check_launch(rc, what);
 }
 
@@ -830,7 +732,7 @@ int fq_int4_skinny_linear_multi_f16(int n, const void* const* x, const void* con
     if (M == 0) return FQ_OK;
     const int rc = fq_launch_gemm_i4_skinny_multi(n, (const uint8_t* const*)x, w_image, M, N, K, (f16* const*)y, (const f16* const*)x_scale,
                                                   (const f16* const*)w_scale, (const f16* const*)bias, (hipStream_t)stream);
-    if (rc == -1000) return fail(FQ_EUNSUPPORTED, "%s: M=%lld K=%d (M <= 128, K %% 64 == 0, K < 131072)", what, (long long)M, K);
+    if (rc == FQ_LAUNCH_NO_KERNEL) return fail(FQ_EUNSUPPORTED, "%s: M=%lld K=%d (M <= 128, K %% 64 == 0, K < 131072)", what, (long long)M, K);
     return check_launch(rc, what);
 }
 
@@ -866,7 +768,7 @@ int fq_kron64_linear_multi_f16(const void* x, int rmsnorm, float rms_eps, const 
     rc = fq_launch_kron64_linear((const f16*)x, workspace, M, rms_eps, rmsnorm != 0, flags & (FQ_NO_CLAMP0 | FQ_ROUND_Y_F16), n, w_image,
                                  (const f16* const*)w_scale, (const f16* const*)bias, sig_max, sig_min, N, (f16* const*)y, cu_count(),
                                  (hipStream_t)stream);
-    if (rc == -1000) return fail(FQ_EUNSUPPORTED, "%s: shape not covered", what);
+    if (rc == FQ_LAUNCH_NO_KERNEL) return fail(FQ_EUNSUPPORTED, "%s: shape not covered", what);
     return check_launch(rc, what);
 }
 
@@ -887,7 +789,7 @@ int fq_block_linear_f16(const void* x, const void* P, int64_t M, int R, int C, f
     if (N & 31) return fail(FQ_EUNSUPPORTED, "%s: N=%d is not a multiple of 32", what, N);
     const int rc = fq_launch_block_linear((const f16*)x, (const f16*)P, M, R, C, sig_max, sig_min, flags, w_image, (const f16*)w_scale,
                                           (const f16*)bias, N, (f16*)y, cu_count(), (hipStream_t)stream);
-    if (rc == -1000) return fail(FQ_EUNSUPPORTED, "%s: shape not covered", what);
+    if (rc == FQ_LAUNCH_NO_KERNEL) return fail(FQ_EUNSUPPORTED, "%s: shape not covered", what);
     return check_launch(rc, what);
 }
 
@@ -906,7 +808,7 @@ int fq_bf6_gemm_i32(const void* xblob, const void* wblob, int64_t M, int N, int 
     if (!xblob || !wblob || !c) return fail(FQ_EINVAL, "fq_bf6_gemm_i32: NULL pointer");
     const int rc = fq_launch_gemm_bf6((const uint8_t*)xblob, (const uint8_t*)wblob, M, N, K, (int32_t*)c, nullptr, nullptr,
                                       nullptr, nullptr, (hipStream_t)stream);
-    if (rc == -1000) return fail(FQ_EUNSUPPORTED, "fq_bf6_gemm_i32: shape M=%lld N=%d K=%d not covered (K %% 128, N %% 16)", (long long)M, N, K);
+    if (rc == FQ_LAUNCH_NO_KERNEL) return fail(FQ_EUNSUPPORTED, "fq_bf6_gemm_i32: shape M=%lld N=%d K=%d not covered (K %% 128, N %% 16)", (long long)M, N, K);
     return check_launch(rc, "fq_bf6_gemm_i32");
 }
 
@@ -917,7 +819,7 @@ int fq_bf6_linear_f16(const void* xblob, const void* x_scale, const void* wblob,
     if (!xblob || !wblob || !y || !x_scale || !w_scale) return fail(FQ_EINVAL, "fq_bf6_linear_f16: NULL pointer");
     const int rc = fq_launch_gemm_bf6((const uint8_t*)xblob, (const uint8_t*)wblob, M, N, K, nullptr, (f16*)y,
                                       (const f16*)x_scale, (const f16*)w_scale, (const f16*)bias, (hipStream_t)stream);
-    if (rc == -1000) return fail(FQ_EUNSUPPORTED, "fq_bf6_linear_f16: shape M=%lld N=%d K=%d not covered (K %% 128, N %% 16)", (long long)M, N, K);
+    if (rc == FQ_LAUNCH_NO_KERNEL) return fail(FQ_EUNSUPPORTED, "fq_bf6_linear_f16: shape M=%lld N=%d K=%d not covered (K %% 128, N %% 16)", (long long)M, N, K);
     return check_launch(rc, "fq_bf6_linear_f16");
 }
 
@@ -1026,7 +928,7 @@ int fq_hadamard_quant_f16(const void* x, int64_t rows, int n, int K, const void*
     if (rows == 0) return FQ_OK;
     const int rc = fq_launch_hadamard_quant((const f16*)x, rows, n, K, (const f16*)hadK, scale, sig_max, sig_min,
                                             (uint8_t*)q_out, (f16*)scale_out, cu_count(), (hipStream_t)stream);
-    if (rc == -1000)
+    if (rc == FQ_LAUNCH_NO_KERNEL)
         return fail(FQ_EUNSUPPORTED, "fq_hadamard_quant_f16: no fused kernel for n=%d K=%d (use fq_hadamard_f16 + fq_rowquant_f16)", n, K);
     return check_launch(rc, "fq_hadamard_quant_f16");
 }
@@ -1042,7 +944,7 @@ int fq_hadamard_quant_mfma_f16(const void* x, int64_t rows, int n, int K, const 
     if (rows == 0) return FQ_OK;
     const int rc = fq_launch_had_mfma((const f16*)x, rows, n, K, (const f16*)hadK, scale, sig_max, sig_min, (uint8_t*)q_out,
                                       (f16*)scale_out, (f16*)y_out, cu_count(), (hipStream_t)stream);
-    if (rc == -1000) return fail(FQ_EUNSUPPORTED, "%s: n=%d K=%d (n = K * 512 or K * 1024 with K <= 32, K %% 4 == 0)", what, n, K);
+    if (rc == FQ_LAUNCH_NO_KERNEL) return fail(FQ_EUNSUPPORTED, "%s: n=%d K=%d (n = K * 512 or K * 1024 with K <= 32, K %% 4 == 0)", what, n, K);
     return check_launch(rc, what);
 }
 
@@ -1058,7 +960,7 @@ int fq_silu_mul_hadamard_quant_mfma_f16(const void* gate, const void* up, int64_
     FQ_NEED_ALIGN16(what, gate, up, hadK, q_out);
     const int rc = fq_launch_had_mfma((const f16*)gate, rows, n, K, (const f16*)hadK, scale, sig_max, sig_min, (uint8_t*)q_out,
                                       (f16*)scale_out, nullptr, cu_count(), (hipStream_t)stream, (const f16*)up);
-    if (rc == -1000) return fail(FQ_EUNSUPPORTED, "%s: n=%d K=%d (n = K * 512, K <= 32, or K * 1024, K <= 28; K %% 4 == 0)", what, n, K);
+    if (rc == FQ_LAUNCH_NO_KERNEL) return fail(FQ_EUNSUPPORTED, "%s: n=%d K=%d (n = K * 512, K <= 32, or K * 1024, K <= 28; K %% 4 == 0)", what, n, K);
     return check_launch(rc, what);
 }
 
@@ -1074,7 +976,7 @@ int fq_hadamard_quantizer_mfma_f16(const void* x, const void* up, int64_t rows, 
     if (rows == 0) return FQ_OK;
     const int rc = fq_launch_had_mfma((const f16*)x, rows, n, K, (const f16*)hadK, scale, input_clip_ratio, 1.0f, (uint8_t*)q_out,
                                       (f16*)scale_out, (f16*)y_out, cu_count(), (hipStream_t)stream, (const f16*)up, 1);
-    if (rc == -1000) return fail(FQ_EUNSUPPORTED, "%s: n=%d K=%d (n = K * 512, K <= 32, or K * 1024, K <= 28; K %% 4 == 0)", what, n, K);
+    if (rc == FQ_LAUNCH_NO_KERNEL) return fail(FQ_EUNSUPPORTED, "%s: n=%d K=%d (n = K * 512, K <= 32, or K * 1024, K <= 28; K %% 4 == 0)", what, n, K);
     return check_launch(rc, what);
 }
 
@@ -1119,122 +1021,114 @@ int fq_kv_dequant_f16(const void* q, const void* param, int64_t rows, int head_d
     return check_launch(rc, "fq_kv_dequant_f16");
 }
 
-static int kv_geometry_ok(const char* what, int num_layers, int layer_idx, int num_heads, int page_size, int head_dim, int batch) {
-    if (num_layers <= 0 || layer_idx < 0 || layer_idx >= num_layers || num_heads <= 0 || page_size <= 0 || batch <= 0)
+// ---- the paged KV cache ----
+// Every entry point below checks in this order: the cache geometry (kv_view), its own argument rules, NULL pointers and 16-byte alignment
+// (kv_pointers_ok), then the workspace size. Callers tell the failures apart by code and fq_last_error() text, so the order is part of the ABI.
+
+// The cache arguments every paged entry point takes, as the view the launchers take; fails on a geometry no kernel reads.
+static int kv_view(const char* what, FqKvView& c, const void* kv_data, const void* kv_param, const void* kv_indptr, const void* kv_indices,
+                   const void* last_page_offset, int num_layers, int layer_idx, int num_heads, int page_size, int head_dim, int batch_size,
+                   bool f16_pages) {
+    c = {(void*)kv_data, (void*)kv_param, (const int*)kv_indptr, (const int*)kv_indices, (const int*)last_page_offset,
+         num_layers, layer_idx, num_heads, page_size, head_dim, batch_size, f16_pages};
+    if (num_layers <= 0 || layer_idx < 0 || layer_idx >= num_layers || num_heads <= 0 || page_size <= 0 || batch_size <= 0)
         return fail(FQ_EINVAL, "%s: bad cache geometry", what);
     if (head_dim != 64 && head_dim != 128) return fail(FQ_EUNSUPPORTED, "%s: head_dim=%d (64 or 128)", what, head_dim);
     return FQ_OK;
+}
+
+// The view's pointers (params only where the entry reads them: fp16 pages carry none) and the entry's own `required` ones are not NULL;
+// `aligned` (NULL passes) start on 16 bytes. aligned_names: the entry's argument names, as the message lists them.
+static int kv_pointers_ok(const char* what, const FqKvView& c, bool need_params, std::initializer_list<const void*> required,
+                          const char* aligned_names, std::initializer_list<const void*> aligned) {
+    bool null = !c.pages || (need_params && !c.params) || !c.indptr || !c.indices || !c.last_page_offset;
+    for (const void* p : required) null = null || !p;
+    if (null) return fail(FQ_EINVAL, "%s: NULL pointer", what);
+    int i = 0;
+    for (const void* p : aligned) {
+        if (misaligned16(p)) return fail(FQ_EINVAL, "%s: pointer argument %d of {%s} is not 16-byte aligned", what, i, aligned_names);
+        ++i;
+    }
+    return FQ_OK;
+}
+
+static FqKvAttn kv_attn(void* o, const void* q, const void* q_trans, int transpose_out) {
+    FqKvAttn a;
+    a.o = (f16*)o;
+    a.q = (const f16*)q;
+    a.qt = (const f16*)q_trans;
+    a.transpose_out = transpose_out != 0;
+    return a;
+}
+
+// The split count of a decode launch (a.share, a.copies set) into a.splits, the workspace into a.ws; fails where the launch would split and
+// the workspace is smaller than `sizer` (the exported function the caller sized it with) says.
+static int kv_plan_splits(const char* what, const char* sizer, const FqKvView& c, FqKvAttn& a, int seq_hint, void* workspace,
+                          int64_t workspace_bytes) {
+    const int q_heads = c.num_heads / a.copies * a.share;
+    const int64_t need = fq_kv_decode_ws_bytes_gqa(c.batch, q_heads, a.share, c.head_dim);
+    a.ws = (float*)workspace;
+    a.splits = (workspace && need > 0) ? fq_kv_decode_splits(c.batch, fq_kv_decode_wg_heads(c.batch, q_heads, a.share, c.head_dim), seq_hint) : 1;
+    if (a.splits > 1 && workspace_bytes < need)
+        return fail(FQ_EINVAL, "%s: workspace of %lld bytes, %s says %lld", what, (long long)workspace_bytes, sizer, (long long)need);
+    return FQ_OK;
+}
+
+static int kv_append(const char* what, bool f16_pages, void* kv_data, void* kv_param, const void* kv_indptr, const void* kv_indices,
+                     const void* last_page_offset, const void* k, const void* v, const void* k_param, const void* v_param,
+                     const void* seqlen_indptr, int64_t tokens, int num_layers, int layer_idx, int num_heads, int page_size,
+                     int head_dim, int batch_size, int group_size, void* stream) {
+    FqKvView c;
+    int rc = kv_view(what, c, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, num_layers, layer_idx, num_heads, page_size, head_dim,
+                     batch_size, f16_pages);
+    if (rc != FQ_OK) return rc;
+    if (group_size < 1 || num_heads % group_size) return fail(FQ_EINVAL, "%s: group_size=%d must divide num_heads=%d", what, group_size, num_heads);
+    if (tokens < 0) return fail(FQ_EINVAL, "%s: tokens < 0", what);
+    if (!seqlen_indptr && tokens != batch_size) return fail(FQ_EINVAL, "%s: without seqlen_indptr every request appends one token (tokens == batch_size)", what);
+    if (tokens == 0) return FQ_OK;
+    rc = kv_pointers_ok(what, c, true, {k, v, k_param, v_param}, "kv_data, k, v", {kv_data, k, v});
+    if (rc != FQ_OK) return rc;
+    rc = fq_launch_kv_append(c, (const uint8_t*)k, (const uint8_t*)v, (const f16*)k_param, (const f16*)v_param, (const int*)seqlen_indptr, tokens,
+                             group_size, cu_count(), (hipStream_t)stream);
+    return check_launch(rc, what);
 }
 
 int fq_kv_append_i4(void* kv_data, void* kv_param, const void* kv_indptr, const void* kv_indices,
                     const void* last_page_offset, const void* k, const void* v, const void* k_param, const void* v_param,
                     const void* seqlen_indptr, int64_t tokens, int num_layers, int layer_idx, int num_heads, int page_size,
                     int head_dim, int batch_size, int group_size, void* stream) {
-    int rc = kv_geometry_ok("fq_kv_append_i4", num_layers, layer_idx, num_heads, page_size, head_dim, batch_size);
-    if (rc != FQ_OK) return rc;
-    if (group_size < 1 || num_heads % group_size) return fail(FQ_EINVAL, "fq_kv_append_i4: group_size=%d must divide num_heads=%d", group_size, num_heads);
-    if (tokens < 0) return fail(FQ_EINVAL, "fq_kv_append_i4: tokens < 0");
-    if (!seqlen_indptr && tokens != batch_size) return fail(FQ_EINVAL, "fq_kv_append_i4: without seqlen_indptr every request appends one token (tokens == batch_size)");
-    if (tokens == 0) return FQ_OK;
-    if (!kv_data || !kv_param || !kv_indptr || !kv_indices || !last_page_offset || !k || !v || !k_param || !v_param)
-        return fail(FQ_EINVAL, "fq_kv_append_i4: NULL pointer");
-    FQ_NEED_ALIGN16("fq_kv_append_i4", kv_data, k, v);
-    rc = fq_launch_kv_append(kv_data, kv_param, (const int*)kv_indptr, (const int*)kv_indices, (const int*)last_page_offset,
-                             (const uint8_t*)k, (const uint8_t*)v, (const f16*)k_param, (const f16*)v_param,
-                             (const int*)seqlen_indptr, tokens, num_layers, layer_idx, num_heads, page_size, head_dim, batch_size,
-                             group_size, cu_count(), (hipStream_t)stream);
-    return check_launch(rc, "fq_kv_append_i4");
+    return kv_append("fq_kv_append_i4", false, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, k, v, k_param, v_param, seqlen_indptr,
+                     tokens, num_layers, layer_idx, num_heads, page_size, head_dim, batch_size, group_size, stream);
 }
 
 int fq_kv_append_f16(void* kv_data, void* kv_param, const void* kv_indptr, const void* kv_indices,
                      const void* last_page_offset, const void* k, const void* v, const void* k_param, const void* v_param,
                      const void* seqlen_indptr, int64_t tokens, int num_layers, int layer_idx, int num_heads, int page_size,
                      int head_dim, int batch_size, int group_size, void* stream) {
-    int rc = kv_geometry_ok("fq_kv_append_f16", num_layers, layer_idx, num_heads, page_size, head_dim, batch_size);
-    if (rc != FQ_OK) return rc;
-    if (group_size < 1 || num_heads % group_size) return fail(FQ_EINVAL, "fq_kv_append_f16: group_size=%d must divide num_heads=%d", group_size, num_heads);
-    if (tokens < 0) return fail(FQ_EINVAL, "fq_kv_append_f16: tokens < 0");
-    if (!seqlen_indptr && tokens != batch_size) return fail(FQ_EINVAL, "fq_kv_append_f16: without seqlen_indptr every request appends one token (tokens == batch_size)");
-    if (tokens == 0) return FQ_OK;
-    if (!kv_data || !kv_param || !kv_indptr || !kv_indices || !last_page_offset || !k || !v || !k_param || !v_param)
-        return fail(FQ_EINVAL, "fq_kv_append_f16: NULL pointer");
-    FQ_NEED_ALIGN16("fq_kv_append_f16", kv_data, k, v);
-    rc = fq_launch_kv_append(kv_data, kv_param, (const int*)kv_indptr, (const int*)kv_indices, (const int*)last_page_offset,
-                             (const uint8_t*)k, (const uint8_t*)v, (const f16*)k_param, (const f16*)v_param,
-                             (const int*)seqlen_indptr, tokens, num_layers, layer_idx, num_heads, page_size, head_dim, batch_size,
-                             group_size, cu_count(), (hipStream_t)stream, true);
-    return check_launch(rc, "fq_kv_append_f16");
-}
-
-int fq_kv_batch_decode_f16_ex(void* o, const void* q, const void* q_trans, int transpose_out, const void* kv_data,
-                              const void* kv_param, const void* kv_indptr, const void* kv_indices,
-                              const void* last_page_offset, int num_layers, int layer_idx, int num_heads, int page_size,
-                              int head_dim, int batch_size, void* stream) {
-    int rc = kv_geometry_ok("fq_kv_batch_decode_f16", num_layers, layer_idx, num_heads, page_size, head_dim, batch_size);
-    if (rc != FQ_OK) return rc;
-    if (!o || !q || !kv_data || !kv_indptr || !kv_indices || !last_page_offset)
-        return fail(FQ_EINVAL, "fq_kv_batch_decode_f16: NULL pointer");
-    FQ_NEED_ALIGN16("fq_kv_batch_decode_f16", kv_data, q_trans);
-    rc = fq_launch_kv_decode((f16*)o, (const f16*)q, (void*)kv_data, (void*)kv_param, (const int*)kv_indptr,
-                             (const int*)kv_indices, (const int*)last_page_offset, num_layers, layer_idx, num_heads, page_size,
-                             head_dim, batch_size, (const f16*)q_trans, transpose_out != 0, (hipStream_t)stream, true);
-    return check_launch(rc, "fq_kv_batch_decode_f16");
-}
-
-int fq_kv_batch_decode_f16(void* o, const void* q, const void* kv_data, const void* kv_param, const void* kv_indptr,
-                           const void* kv_indices, const void* last_page_offset, int num_layers, int layer_idx,
-                           int num_heads, int page_size, int head_dim, int batch_size, void* stream) {
-    return fq_kv_batch_decode_f16_ex(o, q, nullptr, 0, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, num_layers,
-                                     layer_idx, num_heads, page_size, head_dim, batch_size, stream);
+    return kv_append("fq_kv_append_f16", true, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, k, v, k_param, v_param, seqlen_indptr,
+                     tokens, num_layers, layer_idx, num_heads, page_size, head_dim, batch_size, group_size, stream);
 }
 
 int fq_kv_quant_append_i4(const void* k, const void* v, const void* trans, int64_t tokens, int src_heads, int head_dim,
                           const float* clip, int flags, void* kv_data, void* kv_param, const void* kv_indptr,
                           const void* kv_indices, const void* last_page_offset, int num_layers, int layer_idx,
                           int num_heads, int page_size, int batch_size, int group_size, void* stream) {
-    int rc = kv_geometry_ok("fq_kv_quant_append_i4", num_layers, layer_idx, num_heads, page_size, head_dim, batch_size);
+    const char* what = "fq_kv_quant_append_i4";
+    FqKvView c;
+    int rc = kv_view(what, c, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, num_layers, layer_idx, num_heads, page_size, head_dim,
+                     batch_size, false);
     if (rc != FQ_OK) return rc;
-    if (flags & ~FQ_KV_LAC) return fail(FQ_EINVAL, "fq_kv_quant_append_i4: unknown flags 0x%x", flags);
-    if (tokens < 0 || src_heads <= 0 || tokens % batch_size) return fail(FQ_EINVAL, "fq_kv_quant_append_i4: tokens=%lld must be a multiple of batch_size=%d", (long long)tokens, batch_size);
+    if (flags & ~FQ_KV_LAC) return fail(FQ_EINVAL, "%s: unknown flags 0x%x", what, flags);
+    if (tokens < 0 || src_heads <= 0 || tokens % batch_size) return fail(FQ_EINVAL, "%s: tokens=%lld must be a multiple of batch_size=%d", what, (long long)tokens, batch_size);
     if (group_size < 1 || group_size > 8 || src_heads * group_size != num_heads)
-        return fail(FQ_EINVAL, "fq_kv_quant_append_i4: num_heads=%d must be src_heads=%d x group_size=%d (<= 8)", num_heads, src_heads, group_size);
+        return fail(FQ_EINVAL, "%s: num_heads=%d must be src_heads=%d x group_size=%d (<= 8)", what, num_heads, src_heads, group_size);
     if (tokens == 0) return FQ_OK;
-    if (!k || !v || !kv_data || !kv_param || !kv_indptr || !kv_indices || !last_page_offset)
-        return fail(FQ_EINVAL, "fq_kv_quant_append_i4: NULL pointer");
-    FQ_NEED_ALIGN16("fq_kv_quant_append_i4", k, v, trans, kv_data);
-    const float unit[4] = {1.0f, 1.0f, 1.0f, 1.0f};
-    rc = fq_launch_kv_quant_append((const f16*)k, (const f16*)v, (const f16*)trans, tokens, src_heads, head_dim,
-                                   clip ? clip : unit, (flags & FQ_KV_LAC) != 0, kv_data, kv_param, (const int*)kv_indptr,
-                                   (const int*)kv_indices, (const int*)last_page_offset, num_layers, layer_idx, num_heads,
-                                   page_size, (int)(tokens / batch_size), group_size, cu_count(), (hipStream_t)stream);
-    return check_launch(rc, "fq_kv_quant_append_i4");
-}
-
-int fq_kv_batch_decode_i4_ex(void* o, const void* q, const void* q_trans, int transpose_out, const void* kv_data,
-                             const void* kv_param, const void* kv_indptr, const void* kv_indices,
-                             const void* last_page_offset, int num_layers, int layer_idx, int num_heads, int page_size,
-                             int head_dim, int batch_size, void* stream);
-
-int fq_kv_batch_decode_i4(void* o, const void* q, const void* kv_data, const void* kv_param, const void* kv_indptr,
-                          const void* kv_indices, const void* last_page_offset, int num_layers, int layer_idx,
-                          int num_heads, int page_size, int head_dim, int batch_size, void* stream) {
-    return fq_kv_batch_decode_i4_ex(o, q, nullptr, 0, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, num_layers,
-                                    layer_idx, num_heads, page_size, head_dim, batch_size, stream);
-}
-
-int fq_kv_batch_decode_i4_ex(void* o, const void* q, const void* q_trans, int transpose_out, const void* kv_data,
-                             const void* kv_param, const void* kv_indptr, const void* kv_indices,
-                             const void* last_page_offset, int num_layers, int layer_idx, int num_heads, int page_size,
-                             int head_dim, int batch_size, void* stream) {
-    int rc = kv_geometry_ok("fq_kv_batch_decode_i4", num_layers, layer_idx, num_heads, page_size, head_dim, batch_size);
+    rc = kv_pointers_ok(what, c, true, {k, v}, "k, v, trans, kv_data", {k, v, trans, kv_data});
     if (rc != FQ_OK) return rc;
-    if (!o || !q || !kv_data || !kv_param || !kv_indptr || !kv_indices || !last_page_offset)
-        return fail(FQ_EINVAL, "fq_kv_batch_decode_i4: NULL pointer");
-    FQ_NEED_ALIGN16("fq_kv_batch_decode_i4", kv_data, q_trans);
-    rc = fq_launch_kv_decode((f16*)o, (const f16*)q, (void*)kv_data, (void*)kv_param, (const int*)kv_indptr,
-                             (const int*)kv_indices, (const int*)last_page_offset, num_layers, layer_idx, num_heads, page_size,
-                             head_dim, batch_size, (const f16*)q_trans, transpose_out != 0, (hipStream_t)stream);
-    return check_launch(rc, "fq_kv_batch_decode_i4");
+    const float unit[4] = {1.0f, 1.0f, 1.0f, 1.0f};
+    rc = fq_launch_kv_quant_append(c, (const f16*)k, (const f16*)v, (const f16*)trans, tokens, src_heads, clip ? clip : unit,
+                                   (flags & FQ_KV_LAC) != 0, (int)(tokens / batch_size), group_size, cu_count(), (hipStream_t)stream);
+    return check_launch(rc, what);
 }
 
 int64_t fq_kv_decode_workspace_bytes(int batch_size, int num_heads, int head_dim) {
@@ -1247,46 +1141,89 @@ int64_t fq_kv_decode_workspace_bytes_gqa(int batch_size, int num_kv_heads, int q
     return fq_kv_decode_ws_bytes_gqa(batch_size, num_kv_heads * q_group, q_group, head_dim);
 }
 
+// The decode entry points that append nothing. KV_PLAIN: no workspace, never split; KV_SPLIT: one query head per cache head; KV_GQA: `group`
+// query heads share a cache head; KV_COPIES: `group` consecutive cache heads hold identical rows and one is read for all of them.
+enum KvDecodeKind { KV_PLAIN, KV_SPLIT, KV_GQA, KV_COPIES };
+
+static int kv_decode(KvDecodeKind kind, const char* what, int fp16_cache, void* o, const void* q, const void* q_trans, int transpose_out,
+                     const void* kv_data, const void* kv_param, const void* kv_indptr, const void* kv_indices, const void* last_page_offset,
+                     int num_layers, int layer_idx, int num_heads, int group, int page_size, int head_dim, int batch_size, int seq_hint,
+                     void* workspace, int64_t workspace_bytes, void* stream) {
+    FqKvView c;
+    int rc = kv_view(what, c, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, num_layers, layer_idx, num_heads, page_size, head_dim,
+                     batch_size, fp16_cache != 0);
+    if (rc != FQ_OK) return rc;
+    if (kind == KV_GQA && (group < 1 || group > 64)) return fail(FQ_EINVAL, "%s: q_group=%d out of [1, 64]", what, group);
+    if (kind == KV_COPIES && (group < 1 || group > 8 || num_heads % group))
+        return fail(FQ_EINVAL, "%s: copies=%d must be 1..8 and divide num_heads=%d", what, group, num_heads);
+    rc = kv_pointers_ok(what, c, !fp16_cache, {o, q}, kind == KV_PLAIN ? "kv_data, q_trans" : "kv_data, q_trans, workspace",
+                        {kv_data, q_trans, workspace});
+    if (rc != FQ_OK) return rc;
+    FqKvAttn a = kv_attn(o, q, q_trans, transpose_out);
+    a.share = group;
+    a.copies = kind == KV_COPIES ? group : 1;
+    if (kind != KV_PLAIN) {
+        static const char* const sizer[] = {nullptr, "fq_kv_decode_workspace_bytes", "fq_kv_decode_workspace_bytes_gqa",
+                                            "fq_kv_decode_workspace_bytes_gqa(batch, num_heads / copies, copies, head_dim)"};
+        rc = kv_plan_splits(what, sizer[kind], c, a, seq_hint, workspace, workspace_bytes);
+        if (rc != FQ_OK) return rc;
+    }
+    return check_launch(fq_launch_kv_decode(c, a, (hipStream_t)stream), what);
+}
+
+// (the _ex forms report themselves under the plain entry's name)
+int fq_kv_batch_decode_i4_ex(void* o, const void* q, const void* q_trans, int transpose_out, const void* kv_data,
+                             const void* kv_param, const void* kv_indptr, const void* kv_indices,
+                             const void* last_page_offset, int num_layers, int layer_idx, int num_heads, int page_size,
+                             int head_dim, int batch_size, void* stream) {
+    return kv_decode(KV_PLAIN, "fq_kv_batch_decode_i4", 0, o, q, q_trans, transpose_out, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset,
+                     num_layers, layer_idx, num_heads, 1, page_size, head_dim, batch_size, 0, nullptr, 0, stream);
+}
+
+int fq_kv_batch_decode_i4(void* o, const void* q, const void* kv_data, const void* kv_param, const void* kv_indptr,
+                          const void* kv_indices, const void* last_page_offset, int num_layers, int layer_idx,
+                          int num_heads, int page_size, int head_dim, int batch_size, void* stream) {
+    return fq_kv_batch_decode_i4_ex(o, q, nullptr, 0, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, num_layers,
+                                    layer_idx, num_heads, page_size, head_dim, batch_size, stream);
+}
+
+int fq_kv_batch_decode_f16_ex(void* o, const void* q, const void* q_trans, int transpose_out, const void* kv_data,
+                              const void* kv_param, const void* kv_indptr, const void* kv_indices,
+                              const void* last_page_offset, int num_layers, int layer_idx, int num_heads, int page_size,
+                              int head_dim, int batch_size, void* stream) {
+    return kv_decode(KV_PLAIN, "fq_kv_batch_decode_f16", 1, o, q, q_trans, transpose_out, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset,
+                     num_layers, layer_idx, num_heads, 1, page_size, head_dim, batch_size, 0, nullptr, 0, stream);
+}
+
+int fq_kv_batch_decode_f16(void* o, const void* q, const void* kv_data, const void* kv_param, const void* kv_indptr,
+                           const void* kv_indices, const void* last_page_offset, int num_layers, int layer_idx,
+                           int num_heads, int page_size, int head_dim, int batch_size, void* stream) {
+    return fq_kv_batch_decode_f16_ex(o, q, nullptr, 0, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, num_layers,
+                                     layer_idx, num_heads, page_size, head_dim, batch_size, stream);
+}
+
 int fq_kv_batch_decode_split(int fp16_cache, void* o, const void* q, const void* q_trans, int transpose_out, const void* kv_data,
                              const void* kv_param, const void* kv_indptr, const void* kv_indices, const void* last_page_offset,
                              int num_layers, int layer_idx, int num_heads, int page_size, int head_dim, int batch_size, int seq_hint,
                              void* workspace, int64_t workspace_bytes, void* stream) {
-    const char* what = "fq_kv_batch_decode_split";
-    int rc = kv_geometry_ok(what, num_layers, layer_idx, num_heads, page_size, head_dim, batch_size);
-    if (rc != FQ_OK) return rc;
-    if (!o || !q || !kv_data || (!fp16_cache && !kv_param) || !kv_indptr || !kv_indices || !last_page_offset)
-        return fail(FQ_EINVAL, "%s: NULL pointer", what);
-    FQ_NEED_ALIGN16(what, kv_data, q_trans, workspace);
-    const int64_t need = fq_kv_decode_ws_bytes(batch_size, num_heads, head_dim);
-    const int splits = (workspace && need > 0) ? fq_kv_decode_splits(batch_size, num_heads, seq_hint) : 1;
-    if (splits > 1 && workspace_bytes < need)
-        return fail(FQ_EINVAL, "%s: workspace of %lld bytes, fq_kv_decode_workspace_bytes says %lld", what, (long long)workspace_bytes, (long long)need);
-    rc = fq_launch_kv_decode((f16*)o, (const f16*)q, (void*)kv_data, (void*)kv_param, (const int*)kv_indptr, (const int*)kv_indices,
-                             (const int*)last_page_offset, num_layers, layer_idx, num_heads, page_size, head_dim, batch_size,
-                             (const f16*)q_trans, transpose_out != 0, (hipStream_t)stream, fp16_cache != 0, (float*)workspace, splits);
-    return check_launch(rc, what);
+    return kv_decode(KV_SPLIT, "fq_kv_batch_decode_split", fp16_cache, o, q, q_trans, transpose_out, kv_data, kv_param, kv_indptr, kv_indices,
+                     last_page_offset, num_layers, layer_idx, num_heads, 1, page_size, head_dim, batch_size, seq_hint, workspace, workspace_bytes, stream);
 }
 
 int fq_kv_batch_decode_gqa(int fp16_cache, void* o, const void* q, const void* q_trans, int transpose_out, const void* kv_data,
                            const void* kv_param, const void* kv_indptr, const void* kv_indices, const void* last_page_offset,
                            int num_layers, int layer_idx, int num_kv_heads, int q_group, int page_size, int head_dim, int batch_size, int seq_hint,
                            void* workspace, int64_t workspace_bytes, void* stream) {
-    const char* what = "fq_kv_batch_decode_gqa";
-    int rc = kv_geometry_ok(what, num_layers, layer_idx, num_kv_heads, page_size, head_dim, batch_size);
-    if (rc != FQ_OK) return rc;
-    if (q_group < 1 || q_group > 64) return fail(FQ_EINVAL, "%s: q_group=%d out of [1, 64]", what, q_group);
-    if (!o || !q || !kv_data || (!fp16_cache && !kv_param) || !kv_indptr || !kv_indices || !last_page_offset)
-        return fail(FQ_EINVAL, "%s: NULL pointer", what);
-    FQ_NEED_ALIGN16(what, kv_data, q_trans, workspace);
-    const int q_heads = num_kv_heads * q_group;
-    const int64_t need = fq_kv_decode_ws_bytes_gqa(batch_size, q_heads, q_group, head_dim);
-    const int splits = (workspace && need > 0) ? fq_kv_decode_splits(batch_size, fq_kv_decode_wg_heads(batch_size, q_heads, q_group, head_dim), seq_hint) : 1;
-    if (splits > 1 && workspace_bytes < need)
-        return fail(FQ_EINVAL, "%s: workspace of %lld bytes, fq_kv_decode_workspace_bytes_gqa says %lld", what, (long long)workspace_bytes, (long long)need);
-    rc = fq_launch_kv_decode((f16*)o, (const f16*)q, (void*)kv_data, (void*)kv_param, (const int*)kv_indptr, (const int*)kv_indices,
-                             (const int*)last_page_offset, num_layers, layer_idx, q_heads, page_size, head_dim, batch_size,
-                             (const f16*)q_trans, transpose_out != 0, (hipStream_t)stream, fp16_cache != 0, (float*)workspace, splits, q_group);
-    return check_launch(rc, what);
+    return kv_decode(KV_GQA, "fq_kv_batch_decode_gqa", fp16_cache, o, q, q_trans, transpose_out, kv_data, kv_param, kv_indptr, kv_indices,
+                     last_page_offset, num_layers, layer_idx, num_kv_heads, q_group, page_size, head_dim, batch_size, seq_hint, workspace, workspace_bytes, stream);
+}
+
+int fq_kv_batch_decode_copies(int fp16_cache, void* o, const void* q, const void* q_trans, int transpose_out, const void* kv_data,
+                              const void* kv_param, const void* kv_indptr, const void* kv_indices, const void* last_page_offset,
+                              int num_layers, int layer_idx, int num_heads, int copies, int page_size, int head_dim, int batch_size, int seq_hint,
+                              void* workspace, int64_t workspace_bytes, void* stream) {
+    return kv_decode(KV_COPIES, "fq_kv_batch_decode_copies", fp16_cache, o, q, q_trans, transpose_out, kv_data, kv_param, kv_indptr, kv_indices,
+                     last_page_offset, num_layers, layer_idx, num_heads, copies, page_size, head_dim, batch_size, seq_hint, workspace, workspace_bytes, stream);
 }
 
 int64_t fq_kv_transform_image_bytes(int head_dim) { return fq_kv_timage_bytes(head_dim); }
@@ -1305,31 +1242,35 @@ static int kv_decode_append(const char* what, void* o, const void* q, const void
                             const void* kv_indices, const void* last_page_offset, int num_layers, int layer_idx, int num_kv_heads, int q_group,
                             int page_size, int head_dim, int batch_size, int seq_hint, int read_one_copy, void* workspace, int64_t workspace_bytes, void* stream,
                             const void* cos, const void* sin, bool had = false, float had_scale = 0.0f) {
-    int rc = kv_geometry_ok(what, num_layers, layer_idx, num_kv_heads, page_size, head_dim, batch_size);
+    FqKvView c;
+    int rc = kv_view(what, c, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, num_layers, layer_idx, num_kv_heads, page_size, head_dim,
+                     batch_size, false);
     if (rc != FQ_OK) return rc;
     if (q_group < 1 || q_group > 64) return fail(FQ_EINVAL, "%s: q_group=%d out of [1, 64]", what, q_group);
     if (head_dim != 128 || page_size % 16) return fail(FQ_EUNSUPPORTED, "%s: head_dim=%d, page_size=%d: needs head_dim 128 and page_size %% 16 == 0 (use fq_kv_quant_append_i4 + the decode launch)", what, head_dim, page_size);
     if (src_heads < 1 || num_kv_heads % src_heads || num_kv_heads / src_heads > 8)
         return fail(FQ_EINVAL, "%s: num_kv_heads=%d must be src_heads=%d x a group of at most 8", what, num_kv_heads, src_heads);
-    if (!o || !q || !k_new || !v_new || !kv_data || !kv_param || !kv_indptr || !kv_indices || !last_page_offset)
-        return fail(FQ_EINVAL, "%s: NULL pointer", what);
-    FQ_NEED_ALIGN16(what, kv_data, q_trans, workspace, k_new, v_new, k_trans_image);
+    rc = kv_pointers_ok(what, c, true, {o, q, k_new, v_new}, "kv_data, q_trans, workspace, k_new, v_new, k_trans_image",
+                        {kv_data, q_trans, workspace, k_new, v_new, k_trans_image});
+    if (rc != FQ_OK) return rc;
     if ((cos != nullptr) != (sin != nullptr)) return fail(FQ_EINVAL, "%s: cos and sin go together (both, or neither for no rotary embedding)", what);
     FQ_NEED_ALIGN16(what, cos, sin);
-    const int q_heads = num_kv_heads * q_group;
+    FqKvAttn a = kv_attn(o, q, q_trans, transpose_out);
     // read_one_copy: the num_kv_heads / src_heads cache heads of a source head hold identical rows (this function and fq_kv_quant_append_i4 write
     // them so): the launch reads the first copy for the whole group of query heads (and still writes the new row to every copy)
-    const int copies = (read_one_copy && q_group == 1) ? num_kv_heads / src_heads : 1;
-    const int share = q_group * copies;          // query heads that share one set of rows
-    const int64_t need = fq_kv_decode_ws_bytes_gqa(batch_size, q_heads, share, head_dim);
-    const int splits = (workspace && need > 0) ? fq_kv_decode_splits(batch_size, fq_kv_decode_wg_heads(batch_size, q_heads, share, head_dim), seq_hint) : 1;
-    if (splits > 1 && workspace_bytes < need)
-        return fail(FQ_EINVAL, "%s: workspace of %lld bytes, fq_kv_decode_workspace_bytes_gqa says %lld", what, (long long)workspace_bytes, (long long)need);
-    rc = fq_launch_kv_decode((f16*)o, (const f16*)q, (void*)kv_data, (void*)kv_param, (const int*)kv_indptr, (const int*)kv_indices,
-                             (const int*)last_page_offset, num_layers, layer_idx, q_heads, page_size, head_dim, batch_size,
-                             (const f16*)q_trans, transpose_out != 0, (hipStream_t)stream, false, (float*)workspace, splits, share,
-                             (const f16*)k_new, (const f16*)v_new, k_trans_image, src_heads, copies, (const f16*)cos, (const f16*)sin, had, had_scale);
-    return check_launch(rc, what);
+    a.copies = (read_one_copy && q_group == 1) ? num_kv_heads / src_heads : 1;
+    a.share = q_group * a.copies;
+    a.k_new = (const f16*)k_new;
+    a.v_new = (const f16*)v_new;
+    a.t_image = k_trans_image;
+    a.src_heads = src_heads;
+    a.cos = (const f16*)cos;
+    a.sin = (const f16*)sin;
+    a.had = had;
+    a.had_scale = had_scale;
+    rc = kv_plan_splits(what, "fq_kv_decode_workspace_bytes_gqa", c, a, seq_hint, workspace, workspace_bytes);
+    if (rc != FQ_OK) return rc;
+    return check_launch(fq_launch_kv_decode(c, a, (hipStream_t)stream), what);
 }
 
 int fq_kv_decode_append_i4(void* o, const void* q, const void* q_trans, int transpose_out, const void* k_new, const void* v_new,
@@ -1377,31 +1318,24 @@ int fq_rope_f16(void* q_out, void* k_out, const void* q, const void* k, const vo
                                        k ? k_heads : 0, head_dim, (hipStream_t)stream), what);
 }
 
-int fq_kv_batch_decode_copies(int fp16_cache, void* o, const void* q, const void* q_trans, int transpose_out, const void* kv_data,
-                              const void* kv_param, const void* kv_indptr, const void* kv_indices, const void* last_page_offset,
-                              int num_layers, int layer_idx, int num_heads, int copies, int page_size, int head_dim, int batch_size, int seq_hint,
-                              void* workspace, int64_t workspace_bytes, void* stream) {
-    const char* what = "fq_kv_batch_decode_copies";
-    int rc = kv_geometry_ok(what, num_layers, layer_idx, num_heads, page_size, head_dim, batch_size);
-    if (rc != FQ_OK) return rc;
-    if (copies < 1 || copies > 8 || num_heads % copies) return fail(FQ_EINVAL, "%s: copies=%d must be 1..8 and divide num_heads=%d", what, copies, num_heads);
-    if (!o || !q || !kv_data || (!fp16_cache && !kv_param) || !kv_indptr || !kv_indices || !last_page_offset)
-        return fail(FQ_EINVAL, "%s: NULL pointer", what);
-    FQ_NEED_ALIGN16(what, kv_data, q_trans, workspace);
-    const int64_t need = fq_kv_decode_ws_bytes_gqa(batch_size, num_heads, copies, head_dim);
-    const int splits = (workspace && need > 0) ? fq_kv_decode_splits(batch_size, fq_kv_decode_wg_heads(batch_size, num_heads, copies, head_dim), seq_hint) : 1;
-    if (splits > 1 && workspace_bytes < need)
-        return fail(FQ_EINVAL, "%s: workspace of %lld bytes, fq_kv_decode_workspace_bytes_gqa(batch, num_heads / copies, copies, head_dim) says %lld", what, (long long)workspace_bytes, (long long)need);
-    rc = fq_launch_kv_decode((f16*)o, (const f16*)q, (void*)kv_data, (void*)kv_param, (const int*)kv_indptr, (const int*)kv_indices,
-                             (const int*)last_page_offset, num_layers, layer_idx, num_heads, page_size, head_dim, batch_size,
-                             (const f16*)q_trans, transpose_out != 0, (hipStream_t)stream, fp16_cache != 0, (float*)workspace, splits, copies,
-                             nullptr, nullptr, nullptr, 1, copies);
-    return check_launch(rc, what);
-}
-
 int64_t fq_kv_extend_workspace_bytes(int batch_size, int num_q_heads, int q_len, int head_dim) {
     if (batch_size < 0 || num_q_heads <= 0 || q_len < 1 || (head_dim != 64 && head_dim != 128)) return -1;
     return fq_kv_extend_ws_bytes(batch_size, num_q_heads, q_len, head_dim);
+}
+
+// What fq_kv_batch_extend and fq_kv_chunk_extend check first: q_len, the cache geometry (into c), the q_group / copies rule, head_dim 128.
+static int kv_extend_view(const char* what, FqKvView& c, int fp16_cache, const void* kv_data, const void* kv_param, const void* kv_indptr,
+                          const void* kv_indices, const void* last_page_offset, int num_layers, int layer_idx, int num_cache_heads, int q_group,
+                          int copies, int q_len, int page_size, int head_dim, int batch_size) {
+    if (q_len < 1) return fail(FQ_EINVAL, "%s: q_len=%d must be >= 1", what, q_len);
+    const int rc = kv_view(what, c, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, num_layers, layer_idx, num_cache_heads, page_size,
+                           head_dim, batch_size, fp16_cache != 0);
+    if (rc != FQ_OK) return rc;
+    if (q_group < 1 || q_group > 64 || copies < 1 || copies > 8 || q_group % copies || num_cache_heads % copies)
+        return fail(FQ_EINVAL, "%s: q_group=%d (1..64) must be a multiple of copies=%d (1..8), which must divide num_cache_heads=%d", what, q_group,
+                    copies, num_cache_heads);
+    if (head_dim != 128) return fail(FQ_EUNSUPPORTED, "%s: head_dim=%d (128 only)", what, head_dim);
+    return FQ_OK;
 }
 
 int fq_kv_batch_extend(int fp16_cache, void* o, const void* q, const void* q_trans, int transpose_out, const void* kv_data,
@@ -1409,49 +1343,40 @@ int fq_kv_batch_extend(int fp16_cache, void* o, const void* q, const void* q_tra
                        int layer_idx, int num_cache_heads, int q_group, int copies, int q_len, int page_size, int head_dim, int batch_size,
                        int seq_hint, void* workspace, int64_t workspace_bytes, void* stream) {
     const char* what = "fq_kv_batch_extend";
-    if (q_len < 1) return fail(FQ_EINVAL, "%s: q_len=%d must be >= 1", what, q_len);
-    int rc = kv_geometry_ok(what, num_layers, layer_idx, num_cache_heads, page_size, head_dim, batch_size);
+    FqKvView c;
+    int rc = kv_extend_view(what, c, fp16_cache, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, num_layers, layer_idx, num_cache_heads,
+                            q_group, copies, q_len, page_size, head_dim, batch_size);
     if (rc != FQ_OK) return rc;
-    if (q_group < 1 || q_group > 64 || copies < 1 || copies > 8 || q_group % copies || num_cache_heads % copies)
-        return fail(FQ_EINVAL, "%s: q_group=%d (1..64) must be a multiple of copies=%d (1..8), which must divide num_cache_heads=%d", what, q_group,
-                    copies, num_cache_heads);
-    if (head_dim != 128) return fail(FQ_EUNSUPPORTED, "%s: head_dim=%d (128 only)", what, head_dim);
-    if (!o || !q || !kv_data || (!fp16_cache && !kv_param) || !kv_indptr || !kv_indices || !last_page_offset)
-        return fail(FQ_EINVAL, "%s: NULL pointer", what);
-    FQ_NEED_ALIGN16(what, kv_data, q_trans, workspace);
-    const int q_heads = num_cache_heads / copies * q_group;
-    const int64_t need = fq_kv_extend_ws_bytes(batch_size, q_heads, q_len, head_dim);
+    rc = kv_pointers_ok(what, c, !fp16_cache, {o, q}, "kv_data, q_trans, workspace", {kv_data, q_trans, workspace});
+    if (rc != FQ_OK) return rc;
+    const int64_t need = fq_kv_extend_ws_bytes(batch_size, num_cache_heads / copies * q_group, q_len, head_dim);
     if (workspace && need > 0 && workspace_bytes < need)
         return fail(FQ_EINVAL, "%s: workspace of %lld bytes, fq_kv_extend_workspace_bytes says %lld", what, (long long)workspace_bytes, (long long)need);
-    rc = fq_launch_kv_extend((f16*)o, (const f16*)q, (const f16*)q_trans, transpose_out != 0, (void*)kv_data, kv_param, (const int*)kv_indptr,
-                             (const int*)kv_indices, (const int*)last_page_offset, num_layers, layer_idx, num_cache_heads, q_group, copies,
-                             q_len, page_size, head_dim, batch_size, seq_hint, (float*)workspace, workspace_bytes, (hipStream_t)stream,
-                             fp16_cache != 0);
-    return check_launch(rc, what);
+    FqKvAttn a = kv_attn(o, q, q_trans, transpose_out);
+    a.ws = (float*)workspace;   // (the launcher plans the split itself: its count depends on the tiles of the launch)
+    a.share = q_group;
+    a.copies = copies;
+    return check_launch(fq_launch_kv_extend(c, a, q_len, seq_hint, workspace_bytes, (hipStream_t)stream), what);
 }
 
 int fq_kv_chunk_extend(int fp16_cache, void* o, const void* q, const void* q_trans, int transpose_out, const void* kv_data, const void* kv_param,
                        const void* kv_indptr, const void* kv_indices, const void* last_page_offset, int num_layers, int layer_idx,
                        int num_cache_heads, int q_group, int copies, int q_len, int page_size, int head_dim, int batch_size, void* stream) {
     const char* what = "fq_kv_chunk_extend";
-    if (q_len < 1) return fail(FQ_EINVAL, "%s: q_len=%d must be >= 1", what, q_len);
-    int rc = kv_geometry_ok(what, num_layers, layer_idx, num_cache_heads, page_size, head_dim, batch_size);
+    FqKvView c;
+    int rc = kv_extend_view(what, c, fp16_cache, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, num_layers, layer_idx, num_cache_heads,
+                            q_group, copies, q_len, page_size, head_dim, batch_size);
     if (rc != FQ_OK) return rc;
-    if (q_group < 1 || q_group > 64 || copies < 1 || copies > 8 || q_group % copies || num_cache_heads % copies)
-        return fail(FQ_EINVAL, "%s: q_group=%d (1..64) must be a multiple of copies=%d (1..8), which must divide num_cache_heads=%d", what, q_group,
-                    copies, num_cache_heads);
-    if (head_dim != 128) return fail(FQ_EUNSUPPORTED, "%s: head_dim=%d (128 only)", what, head_dim);
     if (q_group != 1 && q_group != 2 && q_group != 4 && q_group != 8)
         return fail(FQ_EUNSUPPORTED, "%s: q_group=%d (1, 2, 4 or 8; fq_kv_batch_extend takes any group)", what, q_group);
-    if (!o || !q || !kv_data || (!fp16_cache && !kv_param) || !kv_indptr || !kv_indices || !last_page_offset)
-        return fail(FQ_EINVAL, "%s: NULL pointer", what);
-    FQ_NEED_ALIGN16(what, o, q, kv_data, q_trans);
+    rc = kv_pointers_ok(what, c, !fp16_cache, {o, q}, "o, q, kv_data, q_trans", {o, q, kv_data, q_trans});
+    if (rc != FQ_OK) return rc;
     if ((int64_t)q_len * q_group > 0x7FFFFF00 || (int64_t)batch_size * (num_cache_heads / copies) * (((int64_t)q_len * q_group + 127) / 128) > 0x7FFFFFFF)
         return fail(FQ_EINVAL, "%s: batch_size=%d x %d row sets x q_len=%d is more than one launch takes", what, batch_size, num_cache_heads / copies, q_len);
-    rc = fq_launch_kv_chunk_extend((f16*)o, (const f16*)q, (const f16*)q_trans, transpose_out != 0, kv_data, kv_param, (const int*)kv_indptr,
-                                   (const int*)kv_indices, (const int*)last_page_offset, num_layers, layer_idx, num_cache_heads, q_group, copies,
-                                   q_len, page_size, head_dim, batch_size, (hipStream_t)stream, fp16_cache != 0);
-    return check_launch(rc, what);
+    FqKvAttn a = kv_attn(o, q, q_trans, transpose_out);
+    a.share = q_group;
+    a.copies = copies;
+    return check_launch(fq_launch_kv_chunk_extend(c, a, q_len, (hipStream_t)stream), what);
 }
 
 int fq_prefill_attention_f16(void* o, const void* q, const void* q_trans, const void* k, const void* v, const void* seq_start,

@@ -38,6 +38,7 @@
 // Built, measured and dropped (docs/DESIGN_LOG.md 10): E2M3 operands, v_mfma_scale_f32_16x16x128_f8f6f4 with its own operand image,
 // 128-token tiles with two stages and two workgroups per CU, non-temporal output stores, waves of 256 x 64 / 64 x 64.
 #include "fq_gemm_common.hpp"
+#include "fq_launch.hpp"
 #include <type_traits>
 
 namespace {
@@ -480,9 +481,9 @@ int64_t fq_bf6_blob_bytes(int64_t rows, int K) {
     return ((rows + 31) / 32) * (int64_t)(K / 64) * BLOB;
 }
 
-// -1000: K % 64 != 0
+// FQ_LAUNCH_NO_KERNEL: K % 64 != 0
 int fq_launch_i4_to_bf6_multi(int nsrc, const uint8_t* const* q, int64_t rows, int K, int perm, uint8_t* blob, int n_cu, hipStream_t stream) {
-    if ((K & 63) || rows < 1 || nsrc < 1 || nsrc > 4) return -1000;
+    if ((K & 63) || rows < 1 || nsrc < 1 || nsrc > 4) return FQ_LAUNCH_NO_KERNEL;
     ConvSrc srcs;
     for (int p = 0; p < 4; ++p) srcs.s[p] = q[p < nsrc ? p : nsrc - 1];
     const int64_t total = nsrc * ((rows + 31) / 32) * (int64_t)((K / 64 + 1) / 2) * 64;
@@ -550,10 +551,10 @@ int bf6_launch(int64_t n_vblocks, int wg_per_cu, const uint8_t* xb, const uint8_
 
 }  // namespace
 
-// -1000: shape not covered (K % 128 != 0, N % 16 != 0, K > 2^18): use the i8 kernel
+// FQ_LAUNCH_NO_KERNEL: shape not covered (K % 128 != 0, N % 16 != 0, K > 2^18): use the i8 kernel
 int fq_launch_gemm_bf6(const uint8_t* xblob, const uint8_t* wblob, int64_t M, int N, int K, int32_t* c, f16* y,
                        const f16* srow, const f16* scol, const f16* bias, hipStream_t stream) {
-    if ((K & 127) || (N & 15) || K > (1 << 18) || M < 1 || N < 1 || M > (1 << 30)) return -1000;
+    if ((K & 127) || (N & 15) || K > (1 << 18) || M < 1 || N < 1 || M > (1 << 30)) return FQ_LAUNCH_NO_KERNEL;
     GemmOut o;
     o.c = c;
     o.y = y;
@@ -569,12 +570,12 @@ int fq_launch_gemm_bf6(const uint8_t* xblob, const uint8_t* wblob, int64_t M, in
     return bf6_launch<256, 0, 256>(n_vblocks, 1, xblob, wblob, M, N, K, o, none, stream);
 }
 
-// Up to four problems with common M and K in one launch (fq_gemm_bf6_kernel<BM, true>). -1000: shape not covered.
+// Up to four problems with common M and K in one launch (fq_gemm_bf6_kernel<BM, true>). FQ_LAUNCH_NO_KERNEL: shape not covered.
 int fq_launch_gemm_bf6_multi(int n, const uint8_t* const* xblob, const uint8_t* const* wblob, int64_t M, const int* Ns, int K, f16* const* y,
                              const f16* const* srow, const f16* const* scol, const f16* const* bias, hipStream_t stream) {
-    if (n < 1 || n > 4 || (K & 127) || K > (1 << 18) || M < 1 || M > (1 << 30)) return -1000;
+    if (n < 1 || n > 4 || (K & 127) || K > (1 << 18) || M < 1 || M > (1 << 30)) return FQ_LAUNCH_NO_KERNEL;
     for (int p = 0; p < n; ++p)
-        if (Ns[p] < 1 || (Ns[p] & 15)) return -1000;
+        if (Ns[p] < 1 || (Ns[p] & 15)) return FQ_LAUNCH_NO_KERNEL;
     int bm, bn;
     bf6_geometry(M, Ns, n, bf6_cus(), bm, bn);
     GemmMultiArg<true> mp = {};

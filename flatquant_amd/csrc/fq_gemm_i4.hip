@@ -17,6 +17,7 @@
 // The weight rows feed the MFMA A operand with a row permutation (prow) that leaves each lane with 16 CONSECUTIVE n of
 // one output row m: 64-byte (int32) or 32-byte (fp16) contiguous stores.
 #include "fq_gemm_common.hpp"
+#include "fq_launch.hpp"
 
 namespace {
 
@@ -404,10 +405,10 @@ __global__ __launch_bounds__(SK_WAVES * 64) void fq_gemm_i4_skinny_kernel(const 
 
 }  // namespace
 
-// -1000: shape not accepted (K must be a multiple of 32, as deploy.matmul asserts, and below 2^25: a full-scale sum must fit the int32).
+// FQ_LAUNCH_NO_KERNEL: shape not accepted (K must be a multiple of 32, as deploy.matmul asserts, and below 2^25: a full-scale sum must fit the int32).
 int fq_launch_gemm_i4(const uint8_t* X, const uint8_t* W, int64_t M, int N, int K, int32_t* c, f16* y, const f16* srow,
                       const f16* scol, const f16* bias, hipStream_t stream) {
-    if ((K & 31) || K < 32 || K >= FQ_SIMPLE_K_LIMIT || M < 1 || N < 1 || M > (1 << 30)) return -1000;
+    if ((K & 31) || K < 32 || K >= FQ_SIMPLE_K_LIMIT || M < 1 || N < 1 || M > (1 << 30)) return FQ_LAUNCH_NO_KERNEL;
     GemmOut o;
     o.c = c;
     o.y = y;
@@ -431,7 +432,7 @@ int64_t fq_i4_frag_bytes(int N, int K) {
 }
 
 int fq_launch_i4_to_frag(const uint8_t* W, int N, int K, void* img, int n_cu, hipStream_t stream) {
-    if (fq_i4_frag_bytes(N, K) < 0) return -1000;
+    if (fq_i4_frag_bytes(N, K) < 0) return FQ_LAUNCH_NO_KERNEL;
     const int64_t total = (int64_t)((N + 31) / 32) * (K / 64) * 64;
     int64_t blocks = (total + 255) / 256;
     if (blocks > (int64_t)n_cu * 16) blocks = (int64_t)n_cu * 16;
@@ -439,10 +440,10 @@ int fq_launch_i4_to_frag(const uint8_t* W, int N, int K, void* img, int n_cu, hi
     return (int)hipGetLastError();
 }
 
-// -1000: M > 128, K % 64 != 0 or K >= 2^17 (the accumulator carries 256 x the sum; use fq_launch_gemm_i4)
+// FQ_LAUNCH_NO_KERNEL: M > 128, K % 64 != 0 or K >= 2^17 (the accumulator carries 256 x the sum; use fq_launch_gemm_i4)
 int fq_launch_gemm_i4_skinny(const uint8_t* X, const void* wimg, int64_t M, int N, int K, int32_t* c, f16* y, const f16* srow,
                              const f16* scol, const f16* bias, hipStream_t stream) {
-    if (M < 1 || M > 128 || N < 1 || (K & 63) || K < 64 || K >= FQ_I8_K_LIMIT) return -1000;
+    if (M < 1 || M > 128 || N < 1 || (K & 63) || K < 64 || K >= FQ_I8_K_LIMIT) return FQ_LAUNCH_NO_KERNEL;
     GemmOut o;
     o.c = c;
     o.y = y;
@@ -503,15 +504,15 @@ int fq_launch_gemm_i4_skinny_split(const uint8_t* X, const void* wimg, int64_t M
     return (int)hipGetLastError();
 }
 
-// -1000: n not in 1..4, M > 128, K % 64 != 0 or K >= 2^17
+// FQ_LAUNCH_NO_KERNEL: n not in 1..4, M > 128, K % 64 != 0 or K >= 2^17
 int fq_launch_gemm_i4_skinny_multi(int n, const uint8_t* const* X, const void* const* wimg, int64_t M, const int* N, int K, f16* const* y,
                                    const f16* const* srow, const f16* const* scol, const f16* const* bias, hipStream_t stream) {
-    if (n < 1 || n > 4 || M < 1 || M > 128 || (K & 63) || K < 64 || K >= FQ_I8_K_LIMIT) return -1000;
+    if (n < 1 || n > 4 || M < 1 || M > 128 || (K & 63) || K < 64 || K >= FQ_I8_K_LIMIT) return FQ_LAUNCH_NO_KERNEL;
     SkinnyProblems pr = {};
     pr.n = n;
     int tiles = 0;
     for (int p = 0; p < n; ++p) {
-        if (N[p] < 1) return -1000;
+        if (N[p] < 1) return FQ_LAUNCH_NO_KERNEL;
         pr.X[p] = X[p];
         pr.Wimg[p] = reinterpret_cast<const uint4*>(wimg[p]);
         pr.out[p].c = nullptr;

@@ -28,6 +28,7 @@
 // tolerance class for this op (tests/test_gpu_hadamard.py: 2e-3 of the row maximum against matmul_hadU's fixtures), not bit identity;
 // ops.hadamard_quant(fwht_route=True) keeps the bit-identical route.
 #include "fq_common.hpp"
+#include "fq_launch.hpp"
 #ifndef HM_PRIO_MFMA
 #define HM_PRIO_MFMA 2   // s_setprio level of a wave inside phases A / B (see fq_kron_duo.hip). 0 until the K * 1024 build: the rotation-only launches
                          // gain (28672: 220 -> 207 us, 14336: 212 -> 209), the fused Quantizer launches are even (profiles/r04_hadamard_1024.txt)
@@ -489,7 +490,7 @@ __global__ __launch_bounds__(GROUPS * 256) void fq_had512_kernel(const f16* __re
     }
 }
 
-// Returns -1000 when the shape is not one this kernel covers (n = K * 512 or n = K * 1024 with K <= 32, K % 4 == 0, hadK given).
+// Returns FQ_LAUNCH_NO_KERNEL when the shape is not one this kernel covers (n = K * 512 or n = K * 1024 with K <= 32, K % 4 == 0, hadK given).
 // q_out / scale_out may be NULL (rotation only), y_out may be NULL (Quantizer output only). In place (y_out == x) is allowed: a token
 // has landed in LDS completely (vmcnt(0) + the group's first meeting) before any of its rows is stored, and tokens do not overlap.
 template <int NA, int GROUPS>
@@ -522,11 +523,11 @@ int fq_launch_had_mfma(const f16* x, int64_t rows, int n, int K, const f16* hadK
                        uint8_t* q_out, f16* scale_out, f16* y_out, int n_cu, hipStream_t stream, const f16* up, int plain_quantizer) {
     // plain_quantizer: deploy.nn.Quantizer(lac=False) — sig_max is its input_clip_ratio (FQ_RATIO_POST), sig_min unused
     const int rt_flags = plain_quantizer ? FQ_RATIO_POST : FQ_SIG_F16;
-    if (up && (!q_out || y_out)) return -1000;
-    if (K <= 1 || K > 32 || (K & 3) || hadK == nullptr || (n != K * 512 && n != K * 1024)) return -1000;
-    if (!q_out && !y_out) return -1000;
+    if (up && (!q_out || y_out)) return FQ_LAUNCH_NO_KERNEL;
+    if (K <= 1 || K > 32 || (K & 3) || hadK == nullptr || (n != K * 512 && n != K * 1024)) return FQ_LAUNCH_NO_KERNEL;
+    if (!q_out && !y_out) return FQ_LAUNCH_NO_KERNEL;
     // the +-1 / 16 (+-1 / 32) right factor is undone here: y = (1 / sqrt(n)) H x = scale * 16 * (H / 16) x
     if (n == K * 512) return hm_launch<4, HM_NGROUPS>(x, rows, K, hadK, scale * 16.0f, sig_max, sig_min, q_out, scale_out, y_out, up, rt_flags, n_cu, stream);
-    if (K > 28) return -1000;   // (the staging buffer of the two-group geometry holds 224 rows)
+    if (K > 28) return FQ_LAUNCH_NO_KERNEL;   // (the staging buffer of the two-group geometry holds 224 rows)
     return hm_launch<8, 2>(x, rows, K, hadK, scale * 32.0f, sig_max, sig_min, q_out, scale_out, y_out, up, rt_flags, n_cu, stream);
 }

@@ -18,6 +18,7 @@
 //     fp16-in/fp32-accumulate arithmetic of the reference's `hadK @ input` in fp16). The A rows are permuted so
 //     each lane ends with 16 consecutive p of one output row k' -> 32-byte stores.
 #include "fq_common.hpp"
+#include "fq_launch.hpp"
 #include <stdlib.h>
 
 namespace {
@@ -214,20 +215,17 @@ __global__ __launch_bounds__(256) void fq_hadamard_kernel(const f16* __restrict_
 
 }  // namespace
 
-int fq_launch_hadamard_reg(const f16* x, f16* y, int64_t rows, int n, int K, const f16* hadK, float scale, int n_cu,
-                           hipStream_t stream);  // fq_hadamard_reg.hip
-
 int fq_launch_hadamard(const f16* x, f16* y, int64_t rows, int n, int K, const f16* hadK, float scale, int n_cu,
                        hipStream_t stream) {
     {  // register FWHT where it applies (P = 64 ... 512 * 2^q); this file is the general case
         const int rc = fq_launch_hadamard_reg(x, y, rows, n, K, hadK, scale, n_cu, stream);
-        if (rc != -1000) return rc;
+        if (rc != FQ_LAUNCH_NO_KERNEL) return rc;
     }
     HadGeom g;
     g.n = n;
     g.K = K;
     g.P = n / K;
-    if (g.P < 32 || (n & 7) || n > 40960 || K > 192) return -1000;
+    if (g.P < 32 || (n & 7) || n > 40960 || K > 192) return FQ_LAUNCH_NO_KERNEL;
     g.log2P = 0;
     while ((1 << g.log2P) < g.P) ++g.log2P;
     g.KP = (K + 15) / 16 * 16;
@@ -239,12 +237,12 @@ int fq_launch_hadamard(const f16* x, f16* y, int64_t rows, int n, int K, const f
         if (vt > main_bytes) main_bytes = vt;
         // items held in registers across the barrier: n >> W per 256 threads, W >= 1 when log2P > 3
         const int W = g.log2P >= 6 ? 3 : g.log2P - 3;  // width of the last butterfly pass (see kernel)
-        if (((n >> W) + 255) / 256 > 20) return -1000;
+        if (((n >> W) + 255) / 256 > 20) return FQ_LAUNCH_NO_KERNEL;
     }
     main_bytes = (main_bytes + 15) & ~(size_t)15;
     g.frag_off = (int)main_bytes;
     const size_t lds = main_bytes + (K > 1 ? (size_t)(g.KP / 16) * g.KT * 1024 : 0);
-    if (lds > 160 * 1024) return -1000;
+    if (lds > 160 * 1024) return FQ_LAUNCH_NO_KERNEL;
     FQ_RAISE_LDS_CAP(fq_hadamard_kernel, 160 * 1024);
     int per_cu = (int)((160 * 1024) / lds);
     if (per_cu > 4) per_cu = 4;

@@ -21,6 +21,7 @@
 //   hardware transpose read: lane i of a 16-lane group receives column i of the 4 x 16 block its group addresses).
 #include "fq_common.hpp"
 #include "fq_xlane.hpp"
+#include "fq_launch.hpp"
 
 namespace {
 
@@ -395,9 +396,9 @@ int launch_kmix(const f16* x, f16* y, int64_t rows, int K, const f16* hadK, floa
     g.K = K;
     g.KP = (K + 15) / 16 * 16;
     g.KT = (K + 31) / 32;
-    if (QUANT && g.KT > 2) return -1000;  // the fused form keeps a wave's tiles in registers (sized for KT <= 2)
+    if (QUANT && g.KT > 2) return FQ_LAUNCH_NO_KERNEL;  // the fused form keeps a wave's tiles in registers (sized for KT <= 2)
     const size_t lds = (size_t)g.KP * (512 * CH / SUB + 8) * 2 + (size_t)(g.KP / 16) * g.KT * 1024 + 64;
-    if (lds > 160 * 1024) return -1000;
+    if (lds > 160 * 1024) return FQ_LAUNCH_NO_KERNEL;
     auto kern = fq_had_kmix_kernel<CH, QUANT, SILU, SUB>;
     FQ_RAISE_LDS_CAP(kern, 160 * 1024);
     int per_cu = (int)((160 * 1024) / lds);
@@ -413,7 +414,7 @@ int launch_kmix(const f16* x, f16* y, int64_t rows, int K, const f16* hadK, floa
 template <bool QUANT, bool SILU = false>
 int dispatch_reg(const f16* x, f16* y, int64_t rows, int n, int K, const f16* hadK, float scale, const HadQuant& hq,
                  int n_cu, hipStream_t stream) {
-    if (K < 1 || n % K) return -1000;
+    if (K < 1 || n % K) return FQ_LAUNCH_NO_KERNEL;
     const int P = n / K;
     if (K == 1) {
         switch (P) {
@@ -429,9 +430,9 @@ int dispatch_reg(const f16* x, f16* y, int64_t rows, int n, int K, const f16* ha
             if (P == 128) return launch_pow2<1, false, false, 4>(x, y, rows, scale, hq, n_cu, stream);
             if (P == 64) return launch_pow2<1, false, false, 8>(x, y, rows, scale, hq, n_cu, stream);
         }
-        return -1000;
+        return FQ_LAUNCH_NO_KERNEL;
     }
-    if (K > 192) return -1000;
+    if (K > 192) return FQ_LAUNCH_NO_KERNEL;
     if (P == 512) return launch_kmix<1, QUANT, SILU>(x, y, rows, K, hadK, scale, hq, n_cu, stream);
     if (P == 1024) return launch_kmix<2, QUANT, SILU>(x, y, rows, K, hadK, scale, hq, n_cu, stream);
     if (!QUANT && !SILU) {  // 11008 = 172 x 64, 5120 = 40 x 128, 7168 = 28 x 256, 18944 = 148 x 128 ...
@@ -439,12 +440,12 @@ int dispatch_reg(const f16* x, f16* y, int64_t rows, int n, int K, const f16* ha
         if (P == 128) return launch_kmix<1, false, false, 4>(x, y, rows, K, hadK, scale, hq, n_cu, stream);
         if (P == 64) return launch_kmix<1, false, false, 8>(x, y, rows, K, hadK, scale, hq, n_cu, stream);
     }
-    return -1000;
+    return FQ_LAUNCH_NO_KERNEL;
 }
 
 }  // namespace
 
-// Returns -1000 for shapes this file does not cover (the caller falls back to fq_hadamard.hip).
+// Returns FQ_LAUNCH_NO_KERNEL for shapes this file does not cover (the caller falls back to fq_hadamard.hip).
 int fq_launch_hadamard_reg(const f16* x, f16* y, int64_t rows, int n, int K, const f16* hadK, float scale, int n_cu,
                            hipStream_t stream) {
     return dispatch_reg<false>(x, y, rows, n, K, hadK, scale, HadQuant{1.0f, 1.0f, nullptr, nullptr, nullptr, nullptr}, n_cu, stream);
@@ -452,11 +453,11 @@ int fq_launch_hadamard_reg(const f16* x, f16* y, int64_t rows, int n, int K, con
 
 // The power-of-two transform alone with an fp32 result: y32 [vecs, P] = FWHT_P(x [vecs, P]) * scale, P in {64 .. 8192}.
 int fq_launch_fwht_f32(const f16* x, float* y32, int64_t vecs, int P, float scale, int n_cu, hipStream_t stream) {
-    if (y32 == nullptr) return -1000;
+    if (y32 == nullptr) return FQ_LAUNCH_NO_KERNEL;
     return dispatch_reg<false>(x, nullptr, vecs, P, 1, nullptr, scale, HadQuant{1.0f, 1.0f, nullptr, nullptr, nullptr, y32}, n_cu, stream);
 }
 
-// Hadamard + deploy.nn.Quantizer in one launch (no fp16 round trip through HBM). -1000: shape not covered.
+// Hadamard + deploy.nn.Quantizer in one launch (no fp16 round trip through HBM). FQ_LAUNCH_NO_KERNEL: shape not covered.
 int fq_launch_hadamard_quant(const f16* x, int64_t rows, int n, int K, const f16* hadK, float scale, float sig_max,
                              float sig_min, uint8_t* q, f16* scale_out, int n_cu, hipStream_t stream) {
     return dispatch_reg<true>(x, nullptr, rows, n, K, hadK, scale, HadQuant{sig_max, sig_min, q, scale_out, nullptr, nullptr}, n_cu, stream);

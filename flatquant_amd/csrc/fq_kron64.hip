@@ -30,6 +30,7 @@
 // Algorithmic traffic per token: 8192 B read + 2048 B packed + 2 B scale = 10242 B.
 #include "fq_common.hpp"
 #include "fq_gemm_common.hpp"
+#include "fq_launch.hpp"
 
 namespace {
 
@@ -1042,16 +1043,16 @@ __global__ __launch_bounds__(KL_THREADS) void fq_kron64_linear_kernel(const f16*
 
 }  // namespace
 
-// The fused decode launch (fq_kron64_linear_multi_f16): -1000 when the shape is not covered. 
+// The fused decode launch (fq_kron64_linear_multi_f16): FQ_LAUNCH_NO_KERNEL when the shape is not covered. 
 int fq_launch_kron64_linear(const f16* x, const void* prep, int64_t M, float rms_eps, bool rms, int rt_flags, int n, const void* const* wimg,
                             const f16* const* scol, const f16* const* bias, const float* sig_max, const float* sig_min, const int* N,
                             f16* const* y, int n_cu, hipStream_t stream) {
-    if (n < 1 || n > 4 || M < 1 || M > KL_MAXM || prep == nullptr) return -1000;
+    if (n < 1 || n > 4 || M < 1 || M > KL_MAXM || prep == nullptr) return FQ_LAUNCH_NO_KERNEL;
     K64LinProblems pr = {};
     pr.n = n;
     int tiles[4] = {0, 0, 0, 0}, total = 0;
     for (int p = 0; p < n; ++p) {
-        if (N[p] < 32 || (N[p] & 31)) return -1000;
+        if (N[p] < 32 || (N[p] & 31)) return FQ_LAUNCH_NO_KERNEL;
         pr.wimg[p] = reinterpret_cast<const uint4*>(wimg[p]);
         pr.y[p] = y[p];
         pr.scol[p] = scol[p];
@@ -1159,7 +1160,7 @@ static int launch_kron64_any(int flags, const T* x, const T* left, const T* righ
     case (F) | FQ_QUANT_F16:                                                           \
         return launch_kron64<(F) | FQ_QUANT_F16, T>(x, left, right, diag, rows, out, n_cu, stream, prep);
     if (out.rt_flags & FQ_GROUP128) {  // per-128-element scales: packed output, fp32 quantiser arithmetic only
-        if ((flags & FQ_CT_MASK) != FQ_OUT_PACKED) return -1000;
+        if ((flags & FQ_CT_MASK) != FQ_OUT_PACKED) return FQ_LAUNCH_NO_KERNEL;
         if (out.group_offsets != nullptr)
             return launch_kron64<FQ_OUT_PACKED | FQ_K64_G128 | FQ_K64_GROUPED, T>(x, left, right, diag, rows, out, n_cu, stream, prep);
         return launch_kron64<FQ_OUT_PACKED | FQ_K64_G128, T>(x, left, right, diag, rows, out, n_cu, stream, prep);
@@ -1181,7 +1182,7 @@ static int launch_kron64_any(int flags, const T* x, const T* left, const T* righ
             case FQ_OUT_FAKEQUANT | FQ_OUT_TRANSFORM | FQ_QUANT_F16:
                 return launch_kron64<FQ_OUT_FAKEQUANT | FQ_OUT_TRANSFORM | FQ_QUANT_F16 | FQ_K64_GROUPED, T>(x, left, right, diag, rows, out, n_cu, stream, prep);
             default:
-                return -1000;
+                return FQ_LAUNCH_NO_KERNEL;
         }
     }
     switch (flags & FQ_CT_MASK) {
@@ -1194,18 +1195,18 @@ static int launch_kron64_any(int flags, const T* x, const T* left, const T* righ
         // (the RMSNorm-fused launches serve deploy.nn.RMSNorm, an fp16-only module in the reference)
         case FQ_OUT_PACKED | FQ_IN_RMSNORM:
             if constexpr (FqVec<T>::is_f16) return launch_kron64<FQ_OUT_PACKED | FQ_IN_RMSNORM, T>(x, left, right, diag, rows, out, n_cu, stream, prep);
-            return -1000;
+            return FQ_LAUNCH_NO_KERNEL;
         case FQ_OUT_TRANSFORM | FQ_IN_RMSNORM:
             if constexpr (FqVec<T>::is_f16) return launch_kron64<FQ_OUT_TRANSFORM | FQ_IN_RMSNORM, T>(x, left, right, diag, rows, out, n_cu, stream, prep);
-            return -1000;
+            return FQ_LAUNCH_NO_KERNEL;
         case FQ_OUT_TRANSFORM | FQ_OUT_PACKED | FQ_IN_RMSNORM:
             if constexpr (FqVec<T>::is_f16) return launch_kron64<FQ_OUT_TRANSFORM | FQ_OUT_PACKED | FQ_IN_RMSNORM, T>(x, left, right, diag, rows, out, n_cu, stream, prep);
-            return -1000;
+            return FQ_LAUNCH_NO_KERNEL;
         case FQ_OUT_TRANSFORM:
         case FQ_OUT_TRANSFORM | FQ_QUANT_F16:
             return launch_kron64<FQ_OUT_TRANSFORM, T>(x, left, right, diag, rows, out, n_cu, stream, prep);
         default:
-            return -1000;
+            return FQ_LAUNCH_NO_KERNEL;
     }
 #undef FQ_CASE
 }

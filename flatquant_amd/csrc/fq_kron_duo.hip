@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "fq_common.hpp"
+#include "fq_launch.hpp"
 #ifndef FQ_PRIO_MFMA
 #define FQ_PRIO_MFMA 2   // s_setprio level of a wave inside its GEMM phases (0: off)
 #endif
@@ -503,15 +504,15 @@ extern "C" int fq_duo_trace_read(void* dst) {
 }
 #endif
 
-// Returns -1000 when the shape / output set is not one this kernel covers (the caller goes on to the generic kernels).
+// Returns FQ_LAUNCH_NO_KERNEL when the shape / output set is not one this kernel covers (the caller goes on to the generic kernels).
 // ws: fragment workspace already filled by fq_kron_prepare_kernel (rfrag [7][14][64], lfrag [2MT][MT][64]).
 int fq_launch_kron_duo(int flags, const f16* x, const void* ws, const f16* diag, int64_t rows, int M, int N,
                        const FqQuantOut& out, int n_cu, hipStream_t stream) {
-    if (N != DUO_N || M <= 96 || M > 128 || diag != nullptr) return -1000;
-    if ((out.rt_flags & FQ_GROUP128) || out.post_scale != 0.0f) return -1000;
+    if (N != DUO_N || M <= 96 || M > 128 || diag != nullptr) return FQ_LAUNCH_NO_KERNEL;
+    if ((out.rt_flags & FQ_GROUP128) || out.post_scale != 0.0f) return FQ_LAUNCH_NO_KERNEL;
     const bool b = (flags & FQ_DT_BF16) != 0;   // (round 4) bf16 activations and factors: the same kernel on bf16 MFMA
     flags &= ~FQ_DT_BF16;
-    if ((flags & FQ_CT_MASK) != FQ_OUT_PACKED) return -1000;
+    if ((flags & FQ_CT_MASK) != FQ_OUT_PACKED) return FQ_LAUNCH_NO_KERNEL;
     const uint4* w = reinterpret_cast<const uint4*>(ws);
     if (b) return M == 128 ? launch_duo<4, true, bf16>((const bf16*)x, w, rows, M, out, n_cu, stream)
                            : launch_duo<4, false, bf16>((const bf16*)x, w, rows, M, out, n_cu, stream);

@@ -4,6 +4,7 @@
 // kernel and compiled for 3.3 minutes; split, the two halves build in parallel.
 #pragma once
 #include "fq_common.hpp"
+#include "fq_launch.hpp"
 #include <stdlib.h>
 
 // Environment switches exist in measurement builds only (-DFQ_MEASURE, tools/microbench/*.sh): the product library reads
@@ -665,8 +666,8 @@ int launch_fast(int flags, const T* x, const uint4* ws, const T* diag, int64_t r
                 const FqQuantOut& out, int n_cu, hipStream_t stream) {
     constexpr int PITCH = (KS1 * 2) | 1;
     const size_t lds = (size_t)2 * MT * MT * 1024 + (size_t)MT * 32 * PITCH * 16 + (((size_t)M * N / 2 + 15) & ~(size_t)15) + 128;
-    if (lds > 160 * 1024) return -1000;
-    if (G128 != ((out.rt_flags & FQ_GROUP128) != 0)) return -1000;   // (the group epilogue is its own instantiation: registers)
+    if (lds > 160 * 1024) return FQ_LAUNCH_NO_KERNEL;
+    if (G128 != ((out.rt_flags & FQ_GROUP128) != 0)) return FQ_LAUNCH_NO_KERNEL;   // (the group epilogue is its own instantiation: registers)
     auto kern = fq_kron_fast_kernel<MT, NT, KS1, WAVES, OCC, SILU, CTF, NV, T, GM, G128>;
     FQ_RAISE_LDS_CAP(kern, 160 * 1024);
     int per_cu = (int)((160 * 1024) / lds);
@@ -682,7 +683,3 @@ int launch_fast(int flags, const T* x, const uint4* ws, const T* diag, int64_t r
 }  // namespace
 
 static inline int tiles32(int n) { return (n + 31) / 32; }
-int64_t fq_kron_generic_workspace_bytes(int M, int N);
-int fq_launch_kron_prepare(const f16* left, const f16* right, int M, int N, void* workspace, hipStream_t stream, int groups = 1);
-int fq_launch_kron_general(int flags, const f16* x, const void* ws, const f16* diag, int64_t rows, int M, int N,
-                           const FqQuantOut& out, int n_cu, hipStream_t stream);

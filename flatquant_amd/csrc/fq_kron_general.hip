@@ -18,6 +18,7 @@
 // generality path, not a tuned one — 16384 tokens of 128 x 148 take well under a millisecond instead of the 24 ms of the
 // plain-FMA kernel it also replaces.
 #include "fq_common.hpp"
+#include "fq_launch.hpp"
 
 namespace {
 
@@ -419,7 +420,7 @@ int launch_general_l(int flags, const T* x, const uint4* ws, const T* diag, int6
     const size_t xs_bytes = (size_t)MT * 32 * g.pitch * 16;
     const size_t ob = ((size_t)g.M * g.N / 2 + 15) & ~(size_t)15;
     const size_t lds = xs_bytes + ob + 2 * WAVES * sizeof(float) + 48 + (LLDS ? (size_t)2 * MT * MT * 1024 : 0);
-    if (lds > 160 * 1024) return -1000;
+    if (lds > 160 * 1024) return FQ_LAUNCH_NO_KERNEL;
     auto kern = fq_kron_general_kernel<MT, WAVES, LLDS, T>;
     FQ_RAISE_LDS_CAP(kern, 160 * 1024);
     int per_cu = (int)((160 * 1024) / lds);  // workgroups that fit a CU's LDS: they overlap each other's synchronous token load
@@ -437,17 +438,17 @@ template <int MT, int WAVES, typename T>
 int launch_general(int flags, const T* x, const uint4* ws, const T* diag, int64_t rows, const GenGeom& g,
                    const FqQuantOut& out, int n_cu, hipStream_t stream) {
     const int rc = launch_general_l<MT, WAVES, true, T>(flags, x, ws, diag, rows, g, out, n_cu, stream);  // L image in LDS if it fits
-    return rc != -1000 ? rc : launch_general_l<MT, WAVES, false, T>(flags, x, ws, diag, rows, g, out, n_cu, stream);
+    return rc != FQ_LAUNCH_NO_KERNEL ? rc : launch_general_l<MT, WAVES, false, T>(flags, x, ws, diag, rows, g, out, n_cu, stream);
 }
 
 }  // namespace
 
-// Every pair with M <= 256, even N <= 256 and M * N <= 32768. -1000 outside that range.
+// Every pair with M <= 256, even N <= 256 and M * N <= 32768. FQ_LAUNCH_NO_KERNEL outside that range.
 // ws: fragment workspace already filled by fq_kron_prepare_kernel (fq_kron_generic.hip).
 int fq_launch_kron_general(int flags, const f16* x, const void* ws, const f16* diag, int64_t rows, int M, int N,
                            const FqQuantOut& out, int n_cu, hipStream_t stream) {
-    if (M < 1 || N < 2 || (N & 1) || M > 256 || N > 256 || (int64_t)M * N > 32768) return -1000;
-    if (out.rt_flags & FQ_GROUP128) return -1000;
+    if (M < 1 || N < 2 || (N & 1) || M > 256 || N > 256 || (int64_t)M * N > 32768) return FQ_LAUNCH_NO_KERNEL;
+    if (out.rt_flags & FQ_GROUP128) return FQ_LAUNCH_NO_KERNEL;
     GenGeom g;
     g.M = M;
     g.N = N;
@@ -466,7 +467,7 @@ int fq_launch_kron_general(int flags, const f16* x, const void* ws, const f16* d
                          : launch_general<MT_, 8, bf16>(flags, xb, w, db, rows, g, out, n_cu, stream);
         FQ_GNB(1) FQ_GNB(2) FQ_GNB(3) FQ_GNB(4) FQ_GNB(5) FQ_GNB(6) FQ_GNB(7) FQ_GNB(8)
 #undef FQ_GNB
-        return -1000;
+        return FQ_LAUNCH_NO_KERNEL;
     }
 #define FQ_GN(MT_)                                                                                        \
     if (MT == MT_)                                                                                        \
@@ -474,5 +475,5 @@ int fq_launch_kron_general(int flags, const f16* x, const void* ws, const f16* d
                          : launch_general<MT_, 8, f16>(flags, x, w, diag, rows, g, out, n_cu, stream);
     FQ_GN(1) FQ_GN(2) FQ_GN(3) FQ_GN(4) FQ_GN(5) FQ_GN(6) FQ_GN(7) FQ_GN(8)
 #undef FQ_GN
-    return -1000;
+    return FQ_LAUNCH_NO_KERNEL;
 }

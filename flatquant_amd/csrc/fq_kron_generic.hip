@@ -58,17 +58,6 @@ __global__ void fq_kron_prepare_kernel(const f16* __restrict__ left, const f16* 
 
 }  // namespace
 
-int fq_launch_kron_wave(int flags, const f16* x, const void* ws, const f16* diag, int64_t rows, int M, int N,
-                        const FqQuantOut& out, int n_cu, hipStream_t stream);  // fq_kron_wave.hip
-int fq_launch_kron_trio(int flags, const f16* x, const void* ws, const f16* diag, int64_t rows, int M, int N,
-                        const FqQuantOut& out, int n_cu, hipStream_t stream);
-int fq_launch_kron_duo(int flags, const f16* x, const void* ws, const f16* diag, int64_t rows, int M, int N,
-                       const FqQuantOut& out, int n_cu, hipStream_t stream);
-int fq_launch_kron_tiles(int flags, const f16* x, const void* ws, const f16* diag, int64_t rows, int M, int N,
-                         const FqQuantOut& out, int n_cu, hipStream_t stream);   // fq_kron_tiles.hip
-int fq_launch_kron_tall(int flags, const f16* x, const void* ws, const f16* diag, int64_t rows, int M, int N,
-                        const FqQuantOut& out, int n_cu, hipStream_t stream);  // fq_kron_trio.hip
-
 int64_t fq_kron_generic_workspace_bytes(int M, int N) {
     const int MT = tiles32(M), NT = tiles32(N), KS1 = (N + 15) / 16;
     return ((int64_t)NT * KS1 + 2 * (int64_t)MT * MT) * 1024;
@@ -82,17 +71,12 @@ int fq_launch_kron_prepare(const f16* left, const f16* right, int M, int N, void
     return (int)hipGetLastError();
 }
 
-
-// fq_kron_generic2.hip: the bf16 instantiations and the group-128 epilogue instantiations of the same kernel
-int fq_launch_kron_generic_bf16(int flags, const f16* x, const f16* left, const f16* right, const f16* diag, int64_t rows, int M, int N,
-                                const FqQuantOut& out, void* workspace, int64_t workspace_bytes, int n_cu, hipStream_t stream);
-int fq_launch_kron_g128_f16(int flags, const f16* x, const uint4* ws, const f16* diag, int64_t rows, int M, int N, const FqQuantOut& out,
-                            int n_cu, hipStream_t stream);
+// (fq_launch_kron_generic_bf16, fq_launch_kron_g128_f16: fq_kron_generic2.hip, the bf16 and the group-128 epilogue instantiations of the same kernel)
 
 int fq_launch_kron_generic(int flags, const f16* x, const f16* left, const f16* right, const f16* diag,
                            int64_t rows, int M, int N, const FqQuantOut& out, void* workspace,
                            int64_t workspace_bytes, int n_cu, hipStream_t stream) {
-    if (M < 1 || N < 2 || (N & 1) || M > 256 || N > 256 || (int64_t)M * N > 32768) return -1000;
+    if (M < 1 || N < 2 || (N & 1) || M > 256 || N > 256 || (int64_t)M * N > 32768) return FQ_LAUNCH_NO_KERNEL;
     if (flags & FQ_DT_BF16)
         return fq_launch_kron_generic_bf16(flags & ~FQ_DT_BF16, x, left, right, diag, rows, M, N, out, workspace, workspace_bytes, n_cu,
                                            stream);
@@ -101,13 +85,13 @@ int fq_launch_kron_generic(int flags, const f16* x, const f16* left, const f16* 
     const bool no_wave = (flags & FQ_NO_WAVE_KERNEL) != 0 || out.post_scale != 0.0f;  // (the wave kernels take no post_scale)
     flags &= ~FQ_NO_WAVE_KERNEL;
     if (flags & FQ_IN_SILU_MUL) {  // fused for the down_proj shapes only; said before any workspace complaint
-        if (!spec) return -1000;
+        if (!spec) return FQ_LAUNCH_NO_KERNEL;
         const int mt = tiles32(M), nt = tiles32(N), ks = (N + 15) / 16;
         if (!((mt == 4 && nt == 4 && ks == 8) || (mt == 3 && nt == 4 && ks == 8) || (mt == 4 && nt == 7 && ks == 14) ||
               (mt == 4 && nt == 8 && ks == 16)))
-            return -1000;
+            return FQ_LAUNCH_NO_KERNEL;
     }
-    if (!workspace || workspace_bytes < fq_kron_generic_workspace_bytes(M, N)) return -1001;
+    if (!workspace || workspace_bytes < fq_kron_generic_workspace_bytes(M, N)) return FQ_LAUNCH_NEED_WS;
     KronGeom g;
     g.M = M;
     g.N = N;
@@ -123,7 +107,7 @@ int fq_launch_kron_generic(int flags, const f16* x, const f16* left, const f16* 
     flags &= ~FQ_WS_PREPARED;
     if (flags & FQ_IN_SILU_MUL) {  // x_up * silu(x_gate) formed while the token is staged: the down_proj shapes (MT >= 3)
         flags &= ~FQ_IN_SILU_MUL;
-        if (diag != nullptr || out.in2 == nullptr) return -1000;
+        if (diag != nullptr || out.in2 == nullptr) return FQ_LAUNCH_NO_KERNEL;
 #define FQ_FS(MT_, NT_, KS1_, W_, OCC_)                                                                          \
     if (MT == MT_ && NT == NT_ && g.KS1 == KS1_) {                                                              \
         if ((flags & FQ_CT_MASK) == FQ_OUT_PACKED && !fq_measure_env("FQ_KRON_NO_CTF"))                                 \
@@ -141,42 +125,42 @@ int fq_launch_kron_generic(int flags, const f16* x, const f16* left, const f16* 
             return launch_fast<4, 4, 8, FQ_FS_DECODE_W, 1, true, FQ_OUT_PACKED>(flags, x, ws, diag, rows, M, N, out, n_cu, stream);
         FQ_FS(4, 4, 8, 4, 2) FQ_FS(3, 4, 8, 4, 2) FQ_FS(4, 7, 14, 8, 1) FQ_FS(4, 8, 16, 8, 1)
 #undef FQ_FS
-        return -1000;
+        return FQ_LAUNCH_NO_KERNEL;
     }
     if (flags & FQ_IN_RMSNORM) {   // fused RMSNorm: the wave-per-token kernel (packed output) is the one that has it
-        if (!spec || no_wave || diag != nullptr) return -1000;
+        if (!spec || no_wave || diag != nullptr) return FQ_LAUNCH_NO_KERNEL;
         return fq_launch_kron_wave(flags, x, ws, diag, rows, M, N, out, n_cu, stream);
     }
     if (spec && !no_wave && !fq_measure_env("FQ_KRON_NO_WAVE")) {  // one wave per token where a token fits a wave (packed output only)
         rc = fq_launch_kron_wave(flags, x, ws, diag, rows, M, N, out, n_cu, stream);
-        if (rc != -1000) return rc;
+        if (rc != FQ_LAUNCH_NO_KERNEL) return rc;
     }
     // per-128-element scales: the wave kernel above (N = 64, packed, fp32 accumulator) or the group epilogue of the
     // workgroup-per-token kernel's all-output-sets instantiations (the transform rounded to the activation dtype)
     const bool g128 = (out.rt_flags & FQ_GROUP128) != 0;
-    if (g128 && (!(flags & FQ_ROUND_Y_F16) || !spec)) return -1000;
+    if (g128 && (!(flags & FQ_ROUND_Y_F16) || !spec)) return FQ_LAUNCH_NO_KERNEL;
     if (!g128 && spec && !fq_measure_env("FQ_KRON_NO_TILES")) { // 80 x 112, 86 x 128, 128 x 144, 144 x 192 (round 4): token groups of NT waves
         rc = fq_launch_kron_tiles(flags, x, ws, diag, rows, M, N, out, n_cu, stream);
-        if (rc != -1000) return rc;
+        if (rc != FQ_LAUNCH_NO_KERNEL) return rc;
     }
     if (!g128 && spec && !fq_measure_env("FQ_KRON_NO_TRIO")) {  // 64 < M <= 128, N = 128, packed output: three token groups one phase apart
         rc = fq_launch_kron_trio(flags, x, ws, diag, rows, M, N, out, n_cu, stream);
-        if (rc != -1000) return rc;
+        if (rc != FQ_LAUNCH_NO_KERNEL) return rc;
     }
     if (!g128 && spec && !fq_measure_env("FQ_KRON_NO_DUO")) {   // 96 < M <= 128, N = 224, packed output: two token groups per CU
         rc = fq_launch_kron_duo(flags, x, ws, diag, rows, M, N, out, n_cu, stream);
-        if (rc != -1000) return rc;
+        if (rc != FQ_LAUNCH_NO_KERNEL) return rc;
     }
     if (!g128 && spec && !fq_measure_env("FQ_KRON_NO_TALL")) {  // 64 < M <= 192, N = 64, packed output: a wave per ROW tile (172 x 64: Hadamard 11008)
         rc = fq_launch_kron_tall(flags, x, ws, diag, rows, M, N, out, n_cu, stream);
-        if (rc != -1000) return rc;
+        if (rc != FQ_LAUNCH_NO_KERNEL) return rc;
     }
 #ifdef FQ_MEASURE
     if (const char* dbg = getenv("FQ_KRON_DBG")) flags |= atoi(dbg) & 0x7000;  // measurement: ablation bits of the fast kernel
 #endif
     if (!g128 && N == 148 && !fq_measure_env("FQ_KRON_NO_TILES")) {   // (round 4) 128 x 148 on token groups of five waves
         rc = fq_launch_kron_tiles(flags, x, ws, diag, rows, M, N, out, n_cu, stream);
-        if (rc != -1000) return rc;
+        if (rc != FQ_LAUNCH_NO_KERNEL) return rc;
     }
     // N % 16 != 0 in the workgroup-per-token kernel: the packed-only launch of 96 < M <= 128, N = 148 (18944 = 128 x 148,
     // Qwen2.5-7B ffn); its other output sets, diag and every other such pair: fq_kron_general.hip
@@ -193,7 +177,7 @@ int fq_launch_kron_generic(int flags, const f16* x, const f16* left, const f16* 
             rc = launch_fast<MT_, NT_, KS1_, W_, OCC_, false, (MT_ >= 3 ? (FQ_OUT_PACKED | FQ_QUANT_F16) : -1)>(flags, x, ws, diag, rows, M, N, out, n_cu, stream); \
         else                                                                                             \
             rc = launch_fast<MT_, NT_, KS1_, W_, OCC_>(flags, x, ws, diag, rows, M, N, out, n_cu, stream); \
-        if (rc != -1000) return rc;                                                                      \
+        if (rc != FQ_LAUNCH_NO_KERNEL) return rc;                                                                      \
     }
 #ifndef FQ_GEN_OCC2
 #define FQ_GEN_OCC2 2   // MT = 2 shapes (measurement knobs): workgroups per CU, waves per workgroup
@@ -211,6 +195,6 @@ int fq_launch_kron_generic(int flags, const f16* x, const f16* left, const f16* 
         FQ_F(6, 6, 11, 8, 1)  // 168 x 176 = 29568 (Qwen2.5-72B ffn)
 #undef FQ_F
     }
-    if (g128) return -1000;   // (the general kernel has no group epilogue)
+    if (g128) return FQ_LAUNCH_NO_KERNEL;   // (the general kernel has no group epilogue)
     return fq_launch_kron_general(flags, x, ws, diag, rows, M, N, out, n_cu, stream);
 }

@@ -20,6 +20,7 @@
 // and the low-half form's v_min3_u16 issues at half rate (tools/microbench/vrate.hip) — 164 -> 178 us with it (profiles/r04_quant_lo_ab.txt)
 #define FQ_QUANT_LO 0
 #include "fq_common.hpp"
+#include "fq_launch.hpp"
 
 namespace {
 
@@ -329,20 +330,20 @@ int launch_tall(const f16* x, const uint4* ws, int64_t rows, int M, const FqQuan
 
 }  // namespace
 
-// Returns -1000 when the shape / output set is not one this kernel covers (the caller goes on to the generic kernels).
+// Returns FQ_LAUNCH_NO_KERNEL when the shape / output set is not one this kernel covers (the caller goes on to the generic kernels).
 // ws: fragment workspace already filled by fq_kron_prepare_kernel (rfrag [2][4][64], lfrag [2MT][MT][64]).
 int fq_launch_kron_tall(int flags, const f16* x, const void* ws, const f16* diag, int64_t rows, int M, int N,
                         const FqQuantOut& out, int n_cu, hipStream_t stream) {
-    if (N != TALL_N || M <= 64 || M > 192 || diag != nullptr) return -1000;
-    if ((out.rt_flags & FQ_GROUP128) || out.ws_group_stride != 0) return -1000;
+    if (N != TALL_N || M <= 64 || M > 192 || diag != nullptr) return FQ_LAUNCH_NO_KERNEL;
+    if ((out.rt_flags & FQ_GROUP128) || out.ws_group_stride != 0) return FQ_LAUNCH_NO_KERNEL;
     const int ct = flags & FQ_CT_MASK, cq = ct & ~FQ_OUT_TRANSFORM;
     const bool yout = (ct & FQ_OUT_TRANSFORM) != 0;
     // (round 4) the transform ALONE (kronecker_matmul; the rotation of matmul_hadU_cuda run as a Kronecker pair): the fp16-epilogue
     // instantiation with no clip set — the quantiser loop does not run, the rounded pairs go out as they are
     const bool yonly = yout && (cq & ~FQ_QUANT_F16) == 0 && out.n_clips == 0;
     const bool h16 = yonly || (cq == (FQ_OUT_PACKED | FQ_QUANT_F16) && (flags & FQ_ROUND_Y_F16));
-    if (cq != FQ_OUT_PACKED && !h16) return -1000;
-    if (yout && out.y == nullptr) return -1000;
+    if (cq != FQ_OUT_PACKED && !h16) return FQ_LAUNCH_NO_KERNEL;
+    if (yout && out.y == nullptr) return FQ_LAUNCH_NO_KERNEL;
     const uint4* wp = reinterpret_cast<const uint4*>(ws);
     const int MT = (M + 31) / 32;
 #define FQ_TALL(MT_)                                                                                              \
@@ -355,5 +356,5 @@ int fq_launch_kron_tall(int flags, const f16* x, const void* ws, const f16* diag
     }
     FQ_TALL(3) FQ_TALL(4) FQ_TALL(5) FQ_TALL(6)
 #undef FQ_TALL
-    return -1000;
+    return FQ_LAUNCH_NO_KERNEL;
 }

@@ -29,6 +29,7 @@
 #define FQ_PRIO_MFMA 2   // s_setprio level of a wave inside its GEMM phases (0: off); see fq_kron_duo.hip
 #endif
 #include "fq_dma.hpp"
+#include "fq_launch.hpp"
 
 namespace {
 
@@ -512,7 +513,7 @@ int launch_tiles(bool is_bf16, const f16* x, const uint4* ws, int64_t rows, int 
 
 }  // namespace
 
-// Returns -1000 when the shape / output set is not one this kernel covers (the caller goes on to the workgroup-per-token kernel).
+// Returns FQ_LAUNCH_NO_KERNEL when the shape / output set is not one this kernel covers (the caller goes on to the workgroup-per-token kernel).
 // ws: fragment workspace already filled by fq_kron_prepare_kernel (rfrag [NT][KS1][64], lfrag [2MT][MT][64]).
 // flags & FQ_DT_BF16: bf16 activations and factors (the same geometry; bf16 MFMA and rounding points). On bf16 this kernel also takes
 // N = 128 (112 x 128, 86 x 128: fq_kron_trio.hip is fp16-only) — three groups of four waves, as there.
@@ -520,7 +521,7 @@ int fq_launch_kron_tiles(int flags, const f16* x, const void* ws, const f16* dia
                          const FqQuantOut& out, int n_cu, hipStream_t stream) {
     const bool b = (flags & FQ_DT_BF16) != 0;
     flags &= ~FQ_DT_BF16;
-    if (diag != nullptr || (out.rt_flags & FQ_GROUP128)) return -1000;
+    if (diag != nullptr || (out.rt_flags & FQ_GROUP128)) return FQ_LAUNCH_NO_KERNEL;
     const uint4* w = reinterpret_cast<const uint4*>(ws);
     const int lks = (M + 15) >> 4;
 #ifndef TILES_N64
@@ -534,11 +535,11 @@ int fq_launch_kron_tiles(int flags, const f16* x, const void* ws, const f16* dia
         const bool yout = (ct & FQ_OUT_TRANSFORM) != 0;
         const bool yonly = yout && (cq & ~FQ_QUANT_F16) == 0 && out.n_clips == 0;
         const bool h16 = yonly || (cq == (FQ_OUT_PACKED | FQ_QUANT_F16) && (flags & FQ_ROUND_Y_F16));
-        if (yout && (out.y == nullptr || !h16)) return -1000;
-        if (!h16 && cq != FQ_OUT_PACKED) return -1000;
+        if (yout && (out.y == nullptr || !h16)) return FQ_LAUNCH_NO_KERNEL;
+        if (!h16 && cq != FQ_OUT_PACKED) return FQ_LAUNCH_NO_KERNEL;
         // (measured, profiles/r05_tall_on_tiles.txt) the rotation ALONE (no clip set: 4 d bytes per token, 32-byte pieces of 128-byte rows from every
         // lane) is slower here than on the row-split kernel at six row tiles — 172 x 64: 180 against 171 us — and level or faster below
-        if (yonly && M > 160) return -1000;
+        if (yonly && M > 160) return FQ_LAUNCH_NO_KERNEL;
         FqQuantOut o2 = out;
         if (!yout) o2.y = nullptr;   // (the kernel writes the transform whenever out.y is given)
         const int MT = (M + 31) / 32;
@@ -552,9 +553,9 @@ int fq_launch_kron_tiles(int flags, const f16* x, const void* ws, const f16* dia
 #endif
         FQ_T64(3, 5, 4) FQ_T64(3, 6, 4) FQ_T64(4, 7, 4) FQ_T64(4, 8, 4) FQ_T64(5, 9, 4) FQ_T64(5, 10, 4) FQ_T64(6, 11, TILES_G64) FQ_T64(6, 12, 3)
 #undef FQ_T64
-        return -1000;
+        return FQ_LAUNCH_NO_KERNEL;
     }
-    if ((flags & FQ_CT_MASK) != FQ_OUT_PACKED) return -1000;
+    if ((flags & FQ_CT_MASK) != FQ_OUT_PACKED) return FQ_LAUNCH_NO_KERNEL;
     if (N == 112 && M > 64 && M <= 96) {   // 80 x 112: four groups of four waves
         return lks == 5 ? launch_tiles<3, 4, 112, TILES_G112, 5, false>(b, x, w, rows, M, out, n_cu, stream)
                         : launch_tiles<3, 4, 112, TILES_G112, 6, false>(b, x, w, rows, M, out, n_cu, stream);
@@ -587,5 +588,5 @@ int fq_launch_kron_tiles(int flags, const f16* x, const void* ws, const f16* dia
         return lks == 7 ? launch_tiles_t<4, 4, 128, 3, 7, false, bf16>((const bf16*)x, w, rows, M, out, n_cu, stream)
                         : launch_tiles_t<4, 4, 128, 3, 8, false, bf16>((const bf16*)x, w, rows, M, out, n_cu, stream);
     }
-    return -1000;
+    return FQ_LAUNCH_NO_KERNEL;
 }

@@ -29,6 +29,7 @@
 #define FQ_PRIO_MFMA 2   // s_setprio level of a wave inside its GEMM phases (0: off)
 #endif
 #include "fq_dma.hpp"
+#include "fq_launch.hpp"
 
 namespace {
 
@@ -418,15 +419,15 @@ extern "C" int fq_trio_trace_read(void* dst) {
 }
 #endif
 
-// Returns -1000 when the shape / output set is not one this kernel covers (the caller goes on to the generic kernels).
+// Returns FQ_LAUNCH_NO_KERNEL when the shape / output set is not one this kernel covers (the caller goes on to the generic kernels).
 // ws: fragment workspace already filled by fq_kron_prepare_kernel (rfrag [4][8][64], lfrag [2MT][MT][64]).
 int fq_launch_kron_trio(int flags, const f16* x, const void* ws, const f16* diag, int64_t rows, int M, int N,
                         const FqQuantOut& out, int n_cu, hipStream_t stream) {
-    if (N != 128 || M <= 64 || M > 128 || diag != nullptr) return -1000;
-    if (out.rt_flags & FQ_GROUP128) return -1000;
+    if (N != 128 || M <= 64 || M > 128 || diag != nullptr) return FQ_LAUNCH_NO_KERNEL;
+    if (out.rt_flags & FQ_GROUP128) return FQ_LAUNCH_NO_KERNEL;
     const int ct = flags & FQ_CT_MASK;
     const bool h16 = ct == (FQ_OUT_PACKED | FQ_QUANT_F16) && (flags & FQ_ROUND_Y_F16);
-    if (ct != FQ_OUT_PACKED && !h16) return -1000;
+    if (ct != FQ_OUT_PACKED && !h16) return FQ_LAUNCH_NO_KERNEL;
     const uint4* w = reinterpret_cast<const uint4*>(ws);
     if (M > 96) return h16 ? launch_trio<4, true>(x, w, rows, M, out, n_cu, stream) : launch_trio<4, false>(x, w, rows, M, out, n_cu, stream);
     return h16 ? launch_trio<3, true>(x, w, rows, M, out, n_cu, stream) : launch_trio<3, false>(x, w, rows, M, out, n_cu, stream);

@@ -24,6 +24,7 @@
 // that used to run the workgroup-per-token kernel (64 x 128: 117 us against 77).
 #include "fq_common.hpp"
 #include "fq_dma.hpp"
+#include "fq_launch.hpp"
 
 namespace {
 
@@ -471,7 +472,7 @@ int launch_wave(const T* x, const uint4* ws, int64_t rows, int M, const FqQuantO
 
 }  // namespace
 
-// Returns -1000 when the shape / output set is not one this kernel covers (the caller falls back to the generic one).
+// Returns FQ_LAUNCH_NO_KERNEL when the shape / output set is not one this kernel covers (the caller falls back to the generic one).
 // ws: fragment workspace already filled by fq_kron_prepare_kernel (rfrag [NT][KS1][64], lfrag [2MT][MT][64]).
 template <typename T>
 static int launch_kron_wave_t(int flags, const T* x, const void* ws, const void* diag, int64_t rows, int M, int N,
@@ -484,13 +485,13 @@ static int launch_kron_wave_t(int flags, const T* x, const void* ws, const void*
     const bool os_ok = N / 16 <= WAVE_OS_MAXKS;
     const bool fq_only = os_ok && ct == FQ_OUT_FAKEQUANT && !rms && !(out.rt_flags & FQ_GROUP128);      // (round 4) 16-bit outputs, fp32 quantiser
     const bool y_only = os_ok && (ct == FQ_OUT_TRANSFORM || ct == (FQ_OUT_TRANSFORM | FQ_QUANT_F16)) && !rms && !(out.rt_flags & FQ_GROUP128) && out.n_clips == 0;
-    if ((ct != FQ_OUT_PACKED && !fq_only && !y_only) || diag != nullptr) return -1000;
-    if ((fq_only && !out.fq[0]) || (y_only && !out.y)) return -1000;
-    if (M < 1 || M > 64 || (N & 15) || ((M * (N / 8)) & 63)) return -1000;
-    if ((out.rt_flags & FQ_GROUP128) && (N != 64 || (M & 1))) return -1000;  // groups = pairs of 64-element rows
+    if ((ct != FQ_OUT_PACKED && !fq_only && !y_only) || diag != nullptr) return FQ_LAUNCH_NO_KERNEL;
+    if ((fq_only && !out.fq[0]) || (y_only && !out.y)) return FQ_LAUNCH_NO_KERNEL;
+    if (M < 1 || M > 64 || (N & 15) || ((M * (N / 8)) & 63)) return FQ_LAUNCH_NO_KERNEL;
+    if ((out.rt_flags & FQ_GROUP128) && (N != 64 || (M & 1))) return FQ_LAUNCH_NO_KERNEL;  // groups = pairs of 64-element rows
     const int MT = (M + 31) / 32, KS1 = N / 16;
     const uint4* w = reinterpret_cast<const uint4*>(ws);
-    if (rms && !FqVec<T>::is_f16) return -1000;   // (deploy.nn.RMSNorm is an fp16 module: no bf16 instantiation with the norm)
+    if (rms && !FqVec<T>::is_f16) return FQ_LAUNCH_NO_KERNEL;   // (deploy.nn.RMSNorm is an fp16 module: no bf16 instantiation with the norm)
 #define FQ_W(MT_, NT_, KS1_, W_)                                                                          \
     if (MT == MT_ && KS1 == KS1_) {                                                                      \
         if constexpr (FqVec<T>::is_f16) {                                                                \
@@ -506,7 +507,7 @@ static int launch_kron_wave_t(int flags, const T* x, const void* ws, const void*
     FQ_W(2, 2, 4, 16)   // 56x64, (64x64 stays with fq_kron64.hip)
     FQ_W(1, 2, 4, 16)   // 32x64
 #undef FQ_W
-    return -1000;
+    return FQ_LAUNCH_NO_KERNEL;
 }
 
 int fq_launch_kron_wave(int flags, const f16* x, const void* ws, const f16* diag, int64_t rows, int M, int N,
@@ -517,7 +518,7 @@ int fq_launch_kron_wave(int flags, const f16* x, const void* ws, const f16* diag
 // the bf16 instantiations (called from fq_launch_kron_generic_bf16, fq_kron_generic2.hip; 64 x 64 stays with fq_kron64.hip)
 int fq_launch_kron_wave_bf16(int flags, const void* x, const void* ws, const void* diag, int64_t rows, int M, int N,
                              const FqQuantOut& out, int n_cu, hipStream_t stream) {
-    if (M == 64 && N == 64) return -1000;
-    if (out.rt_flags & FQ_GROUP128) return -1000;   // (bf16 group-128 launches: the workgroup kernel's group epilogue)
+    if (M == 64 && N == 64) return FQ_LAUNCH_NO_KERNEL;
+    if (out.rt_flags & FQ_GROUP128) return FQ_LAUNCH_NO_KERNEL;   // (bf16 group-128 launches: the workgroup kernel's group epilogue)
     return launch_kron_wave_t<bf16>(flags, (const bf16*)x, ws, diag, rows, M, N, out, n_cu, stream);
 }

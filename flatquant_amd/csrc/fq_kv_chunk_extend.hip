@@ -32,6 +32,7 @@
 // rows before it alone (a rescale by exp2(0) and the products of a masked row, p = 0, change no bit), so two launches are bit-identical and
 // a step fed as two consecutive launches equals the one launch.
 #include "fq_kv_common.hpp"
+#include "fq_launch.hpp"
 
 namespace {
 
@@ -372,20 +373,21 @@ __global__ __launch_bounds__(CX_THREADS, 2) void fq_kv_chunk_extend_kernel(CxArg
 
 }  // namespace
 
-int fq_launch_kv_chunk_extend(f16* o, const f16* q, const f16* qt, int transpose_out, const void* kv_data, const void* kv_param, const int* indptr,
-                              const int* indices, const int* last, int num_layers, int layer_idx, int num_cache_heads, int q_group, int copies,
-                              int q_len, int page_size, int head_dim, int batch, hipStream_t stream, bool f16_cache) {
-    if (head_dim != CX_HD || q_len < 1 || copies < 1 || q_group % copies || num_cache_heads % copies || page_size < 1 || batch < 1) return -1000;
+int fq_launch_kv_chunk_extend(const FqKvView& c, const FqKvAttn& at, int q_len, hipStream_t stream) {
+    const int num_cache_heads = c.num_heads, q_group = at.share, copies = at.copies, page_size = c.page_size, head_dim = c.head_dim, batch = c.batch;
+    const bool f16_cache = c.f16_pages;
+    const f16* const qt = at.qt;
+    if (head_dim != CX_HD || q_len < 1 || copies < 1 || q_group % copies || num_cache_heads % copies || page_size < 1 || batch < 1) return FQ_LAUNCH_NO_KERNEL;
     int gshift = 0;
     while (gshift < 4 && (1 << gshift) != q_group) ++gshift;
-    if (gshift > 3) return -1000;                                  // q_group 1 / 2 / 4 / 8
+    if (gshift > 3) return FQ_LAUNCH_NO_KERNEL;                     // q_group 1 / 2 / 4 / 8
     const int NY = num_cache_heads / copies;
     const int64_t nblk = ((int64_t)q_len * q_group + CX_QB - 1) / CX_QB, wgs = (int64_t)batch * NY * nblk;
-    if ((int64_t)q_len * q_group > 0x7FFFFFFF - CX_QB || wgs > 0x7FFFFFFF) return -1000;
+    if ((int64_t)q_len * q_group > 0x7FFFFFFF - CX_QB || wgs > 0x7FFFFFFF) return FQ_LAUNCH_NO_KERNEL;
     int pshift = -1;
     if ((page_size & (page_size - 1)) == 0) pshift = __builtin_ctz((unsigned)page_size);
-    CxArgs a = {o, q, qt, (const uint8_t*)kv_data, (const uint32_t*)kv_param, indptr, indices, last, num_layers, layer_idx, num_cache_heads, page_size,
-                copies, q_len, NY * q_group, gshift, NY, batch, (int)nblk, transpose_out, pshift};
+    CxArgs a = {at.o, at.q, qt, (const uint8_t*)c.pages, (const uint32_t*)c.params, c.indptr, c.indices, c.last_page_offset, c.num_layers, c.layer_idx,
+                num_cache_heads, page_size, copies, q_len, NY * q_group, gshift, NY, batch, (int)nblk, at.transpose_out, pshift};
     // (the ring is a static array: the compiler's resource report then states the kernel's LDS, and the launch needs no raised cap)
 #define FQ_CX(QT_, F16_) hipLaunchKernelGGL((fq_kv_chunk_extend_kernel<QT_, F16_>), dim3((unsigned)wgs), dim3(CX_THREADS), 0, stream, a);
     if (qt != nullptr) {

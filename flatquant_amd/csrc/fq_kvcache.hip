@@ -32,6 +32,7 @@
 //     20.8 -> 8.6 us (profiles/r05_kvdecode_timing.txt, r05_kvdecode_pmc.txt).
 #include "fq_kv_common.hpp"
 #include "fq_xlane.hpp"
+#include "fq_launch.hpp"
 #include <type_traits>
 
 namespace {
@@ -985,30 +986,29 @@ __global__ __launch_bounds__(NW * 64, (KV_PVM_OCC4 && KV_PV_MFMA && QG == 4 && !
 
 }  // namespace
 
-static PagedKv make_kv(void* kv_data, void* kv_param, const int* indptr, const int* indices, const int* last, int num_layers,
-                       int layer_idx, int num_heads, int page_size, int head_dim, int batch) {
+static PagedKv make_kv(const FqKvView& c, int copies) {
     PagedKv p;
-    p.data = (uint8_t*)kv_data;
-    p.param = (f16*)kv_param;
-    p.indptr = indptr;
-    p.indices = indices;
-    p.last_page_offset = last;
-    p.num_layers = num_layers;
-    p.layer_idx = layer_idx;
-    p.num_heads = num_heads;
-    p.page_size = page_size;
-    p.head_dim = head_dim;
-    p.batch_size = batch;
-    p.copies = 1;
+    p.data = (uint8_t*)c.pages;
+    p.param = (f16*)c.params;
+    p.indptr = c.indptr;
+    p.indices = c.indices;
+    p.last_page_offset = c.last_page_offset;
+    p.num_layers = c.num_layers;
+    p.layer_idx = c.layer_idx;
+    p.num_heads = c.num_heads;
+    p.page_size = c.page_size;
+    p.head_dim = c.head_dim;
+    p.batch_size = c.batch;
+    p.copies = copies;
     return p;
 }
 
-int fq_launch_kv_append(void* kv_data, void* kv_param, const int* indptr, const int* indices, const int* last, const uint8_t* k,
-                        const uint8_t* v, const f16* kparam, const f16* vparam, const int* seqlen_indptr, int64_t total_tokens,
-                        int num_layers, int layer_idx, int num_heads, int page_size, int head_dim, int batch, int group, int n_cu,
-                        hipStream_t stream, bool f16_cache) {
-    if (head_dim % 32 || group < 1 || num_heads % group) return -1000;
-    const PagedKv p = make_kv(kv_data, kv_param, indptr, indices, last, num_layers, layer_idx, num_heads, page_size, head_dim, batch);
+int fq_launch_kv_append(const FqKvView& c, const uint8_t* k, const uint8_t* v, const f16* kparam, const f16* vparam,
+                        const int* seqlen_indptr, int64_t total_tokens, int group, int n_cu, hipStream_t stream) {
+    const int num_heads = c.num_heads, head_dim = c.head_dim;
+    const bool f16_cache = c.f16_pages;
+    if (head_dim % 32 || group < 1 || num_heads % group) return FQ_LAUNCH_NO_KERNEL;
+    const PagedKv p = make_kv(c, 1);
     const int64_t items = total_tokens * num_heads * (f16_cache ? head_dim / 8 : head_dim / 32);
     int64_t blocks = (items + 255) / 256;
     if (blocks > (int64_t)n_cu * 16) blocks = (int64_t)n_cu * 16;
@@ -1069,25 +1069,26 @@ int64_t fq_kv_decode_ws_bytes(int batch, int num_heads, int head_dim) {   // for
     return ((pairs + 3) & ~(int64_t)3) * (int64_t)sizeof(unsigned) + pairs * 16 * (head_dim + 2) * (int64_t)sizeof(float);
 }
 
-int fq_launch_kv_decode(f16* o, const f16* q, void* kv_data, void* kv_param, const int* indptr, const int* indices, const int* last,
-                        int num_layers, int layer_idx, int num_heads, int page_size, int head_dim, int batch, const f16* qt,
-                        int transpose_out, hipStream_t stream, bool f16_cache, float* ws, int splits, int qgroup, const f16* k_new,
-                        const f16* v_new, const void* t_image, int src_heads, int copies, const f16* rope_cos, const f16* rope_sin, bool had, float had_scale) {
-    // num_heads: QUERY heads (q, o); qgroup of them share one set of rows; the cache holds (num_heads / qgroup) * copies heads: copies = 1 and
-    // qgroup = 1 the reference's layout read head by head, copies = 1 and qgroup = g a cache that holds the KV heads once, copies = qgroup = g the
-    // reference's layout (g identical copies per KV head) read ONE copy per group
-    if (splits > 16 || qgroup < 1 || num_heads % qgroup || copies < 1 || copies > 8) return -1000;   // (the merge of the split launch reads at most 16 states: fq_kv_decode_splits never returns more)
-    PagedKv p = make_kv(kv_data, kv_param, indptr, indices, last, num_layers, layer_idx, num_heads / qgroup * copies, page_size, head_dim, batch);
-    p.copies = copies;
+int fq_launch_kv_decode(const FqKvView& c, const FqKvAttn& a, hipStream_t stream) {
+    // (FqKvAttn, fq_launch.hpp, for share / copies) num_heads below: QUERY heads (q, o)
+    const int qgroup = a.share, copies = a.copies, splits = a.splits, src_heads = a.src_heads, transpose_out = a.transpose_out;
+    if (splits > 16 || qgroup < 1 || copies < 1 || copies > 8 || c.num_heads % copies) return FQ_LAUNCH_NO_KERNEL;   // (the merge of the split launch reads at most 16 states: fq_kv_decode_splits never returns more)
+    const int num_heads = c.num_heads / copies * qgroup, page_size = c.page_size, head_dim = c.head_dim, batch = c.batch;
+    const bool f16_cache = c.f16_pages, had = a.had;
+    f16* const o = a.o;
+    const f16 *const q = a.q, *const qt = a.qt, *const k_new = a.k_new, *const v_new = a.v_new, *const rope_cos = a.cos, *const rope_sin = a.sin;
+    const void* const t_image = a.t_image;
+    float* const ws = a.ws;
+    const PagedKv p = make_kv(c, copies);
     const bool split = ws != nullptr && splits > 1;
     // k_new: the step's own row is quantised and appended by this launch (KvNew): INT4 cache, head_dim 128, page_size % 16 == 0 only
     // rope_cos / rope_sin [batch, head_dim]: that launch rotates its queries and the new K row first (fq_kv_decode_append_rope_i4)
-    if ((rope_cos != nullptr) != (rope_sin != nullptr) || (rope_cos != nullptr && k_new == nullptr)) return -1000;
+    if ((rope_cos != nullptr) != (rope_sin != nullptr) || (rope_cos != nullptr && k_new == nullptr)) return FQ_LAUNCH_NO_KERNEL;
     // had: that launch applies the normalised Hadamard rotation (had_scale = 1 / sqrt(head_dim)) to its queries and the new K row instead (fq_kv_decode_append_had_i4):
     // no query transform, no image, no tables
-    if (had && (k_new == nullptr || qt != nullptr || t_image != nullptr || rope_cos != nullptr)) return -1000;
-    KvNew nw = {k_new, v_new, reinterpret_cast<const uint4*>(t_image), src_heads, had ? had_scale : 0.0f, rope_cos, rope_sin};
-    if (k_new != nullptr && (f16_cache || head_dim != 128 || page_size % 16 || v_new == nullptr || src_heads < 1 || (num_heads / qgroup * copies) % src_heads)) return -1000;
+    if (had && (k_new == nullptr || qt != nullptr || t_image != nullptr || rope_cos != nullptr)) return FQ_LAUNCH_NO_KERNEL;
+    KvNew nw = {k_new, v_new, reinterpret_cast<const uint4*>(t_image), src_heads, had ? a.had_scale : 0.0f, rope_cos, rope_sin};
+    if (k_new != nullptr && (f16_cache || head_dim != 128 || page_size % 16 || v_new == nullptr || src_heads < 1 || (num_heads / qgroup * copies) % src_heads)) return FQ_LAUNCH_NO_KERNEL;
     const bool append = k_new != nullptr;
     // (round 6) a shared cache with 2 or 4 query heads per KV head at head_dim 128: ONE workgroup per (request, KV head) serves its query heads
     // from one pass over the rows (fq_kv_decode_kernel<.., QG>); every other geometry: a workgroup per query head
@@ -1133,7 +1134,7 @@ int fq_launch_kv_decode(f16* o, const f16* q, void* kv_data, void* kv_param, con
     } else if (head_dim == 64) {
         if (wide) FQ_DEC(64, 8) else FQ_DEC(64, 4)
     } else {
-        return -1000;
+        return FQ_LAUNCH_NO_KERNEL;
     }
 #undef FQ_DEC
 #undef FQ_DEC2

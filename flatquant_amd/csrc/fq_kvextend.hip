@@ -25,6 +25,7 @@
 // s_v >= 128 (values times 2^11, weight times 2^-11) was built and measured: 442 -> 506 us at 8 x 2048 rows, T = 512
 // (profiles/attn_closed_form.txt); not kept.
 #include "fq_kv_common.hpp"
+#include "fq_launch.hpp"
 #include <type_traits>
 
 namespace {
@@ -458,11 +459,11 @@ int64_t fq_kv_extend_ws_bytes(int batch, int num_q_heads, int q_len, int head_di
     return (int64_t)KX_WS_COUNTERS * (int64_t)sizeof(unsigned) + 256 * 16 * (int64_t)(head_dim + 2) * (int64_t)sizeof(float);
 }
 
-int fq_launch_kv_extend(f16* o, const f16* q, const f16* qt, int transpose_out, void* kv_data, const void* kv_param, const int* indptr,
-                        const int* indices, const int* last, int num_layers, int layer_idx, int num_cache_heads, int q_group, int copies,
-                        int q_len, int page_size, int head_dim, int batch, int seq_hint, float* ws, int64_t ws_bytes, hipStream_t stream,
-                        bool f16_cache) {
-    if (head_dim != KX_HD || q_len < 1 || q_group < 1 || copies < 1 || q_group % copies || num_cache_heads % copies) return -1000;
+int fq_launch_kv_extend(const FqKvView& c, const FqKvAttn& at, int q_len, int seq_hint, int64_t ws_bytes, hipStream_t stream) {
+    const int num_cache_heads = c.num_heads, q_group = at.share, copies = at.copies, page_size = c.page_size, head_dim = c.head_dim, batch = c.batch;
+    const bool f16_cache = c.f16_pages;
+    float* const ws = at.ws;
+    if (head_dim != KX_HD || q_len < 1 || q_group < 1 || copies < 1 || q_group % copies || num_cache_heads % copies) return FQ_LAUNCH_NO_KERNEL;
     const int QH = num_cache_heads / copies * q_group, NY = num_cache_heads / copies;
     const int ntiles = (q_len * q_group + 15) / 16;
     const int64_t wgs = (int64_t)batch * NY * ntiles;
@@ -472,9 +473,9 @@ int fq_launch_kv_extend(f16* o, const f16* q, const f16* qt, int transpose_out, 
     // eight-wave workgroups up to two per CU (the decode's choice); beyond, four waves. A split launch has at most 256 workgroups
     // (kv_extend_splits): always eight waves, so the four-wave kernels are built unsplit only.
     const bool wide = wgs * splits <= 512;
-    if (split && !wide) return -1000;
-    ExtKv p = {(uint8_t*)kv_data, (const f16*)kv_param, indptr, indices, last, num_layers, layer_idx, num_cache_heads, page_size, copies};
-    ExtArgs a = {o, q, qt, ws, q_len, QH, q_group, ntiles, transpose_out};
+    if (split && !wide) return FQ_LAUNCH_NO_KERNEL;
+    ExtKv p = {(uint8_t*)c.pages, (const f16*)c.params, c.indptr, c.indices, c.last_page_offset, c.num_layers, c.layer_idx, num_cache_heads, page_size, copies};
+    ExtArgs a = {at.o, at.q, at.qt, ws, q_len, QH, q_group, ntiles, at.transpose_out};
     const dim3 grid((unsigned)batch, (unsigned)NY, (unsigned)(ntiles * splits));
 #define FQ_EXT4(NW_, UNI_, F16_, SP_)                                                                                  \
     {                                                                                                                 \

@@ -10,6 +10,7 @@
 // exactly where the torch expression does (native _Float16 ops; the fp16 division is the correctly rounded one,
 // fq_common.hpp). V (no transform) takes the same path with the loaded fragments as values.
 #include "fq_kv_common.hpp"
+#include "fq_launch.hpp"
 
 namespace {
 using namespace fqkv;
@@ -277,7 +278,7 @@ int fq_launch_kv_quant(const f16* x, const f16* T, int64_t rows, int hd, float c
     const KvIO io = kv_io_dense(x, cmax, cmin, q, param, y);
     if (hd == 128) return launch_kv<128>(io, T, rows, lac, n_cu, stream);
     if (hd == 64) return launch_kv<64>(io, T, rows, lac, n_cu, stream);
-    return -1000;
+    return FQ_LAUNCH_NO_KERNEL;
 }
 
 // The K transform as the fragment image fq_kv_quant_kernel builds in LDS at the start of every launch ([(s * NTL + nt)][lane] uint4, 32 KB at
@@ -297,16 +298,14 @@ int64_t fq_kv_timage_bytes(int hd) { return (hd == 128 || hd == 64) ? (int64_t)(
 int fq_launch_kv_timage(const f16* T, int hd, void* img, hipStream_t stream) {
     if (hd == 128) hipLaunchKernelGGL(fq_kv_timage_kernel<128>, dim3(1), dim3(256), 0, stream, T, reinterpret_cast<uint4*>(img));
     else if (hd == 64) hipLaunchKernelGGL(fq_kv_timage_kernel<64>, dim3(1), dim3(256), 0, stream, T, reinterpret_cast<uint4*>(img));
-    else return -1000;
+    else return FQ_LAUNCH_NO_KERNEL;
     return (int)hipGetLastError();
 }
 
 // K (transformed when T != nullptr) and V of one layer step, quantised and written straight into the paged cache.
-int fq_launch_kv_quant_append(const f16* k, const f16* v, const f16* T, int64_t tokens, int src_heads, int hd, const float* clip4,
-                              bool lac, void* kv_data, void* kv_param, const int* indptr, const int* indices, const int* last,
-                              int num_layers, int layer_idx, int num_heads, int page_size, int added, int group, int n_cu,
-                              hipStream_t stream) {
-    if (group < 1 || group > 8 || src_heads * group != num_heads || added < 1) return -1000;
+int fq_launch_kv_quant_append(const FqKvView& c, const f16* k, const f16* v, const f16* T, int64_t tokens, int src_heads,
+                              const float* clip4, bool lac, int added, int group, int n_cu, hipStream_t stream) {
+    if (group < 1 || group > 8 || src_heads * group != c.num_heads || added < 1) return FQ_LAUNCH_NO_KERNEL;
     KvIO io = {};
     io.x[0] = k;
     io.x[1] = v;
@@ -314,22 +313,22 @@ int fq_launch_kv_quant_append(const f16* k, const f16* v, const f16* T, int64_t 
     io.cmin[0] = clip4[1];
     io.cmax[1] = clip4[2];
     io.cmin[1] = clip4[3];
-    io.data = (uint8_t*)kv_data;
-    io.pparam = (f16*)kv_param;
-    io.indptr = indptr;
-    io.indices = indices;
-    io.last = last;
-    io.num_layers = num_layers;
-    io.layer_idx = layer_idx;
-    io.num_heads = num_heads;
-    io.page_size = page_size;
+    io.data = (uint8_t*)c.pages;
+    io.pparam = (f16*)c.params;
+    io.indptr = c.indptr;
+    io.indices = c.indices;
+    io.last = c.last_page_offset;
+    io.num_layers = c.num_layers;
+    io.layer_idx = c.layer_idx;
+    io.num_heads = c.num_heads;
+    io.page_size = c.page_size;
     io.added = added;
     io.group = group;
     io.src_heads = src_heads;
     const int64_t rows = tokens * src_heads;
-    if (hd == 128) return launch_kv<128>(io, T, rows, lac, n_cu, stream);
-    if (hd == 64) return launch_kv<64>(io, T, rows, lac, n_cu, stream);
-    return -1000;
+    if (c.head_dim == 128) return launch_kv<128>(io, T, rows, lac, n_cu, stream);
+    if (c.head_dim == 64) return launch_kv<64>(io, T, rows, lac, n_cu, stream);
+    return FQ_LAUNCH_NO_KERNEL;
 }
 
 // ---- the single-matrix transform alone: y = x.reshape(-1, n) @ matrix in the activation's dtype (round 4) ----
@@ -396,7 +395,7 @@ static int launch_rowmm(const T* x, const T* Tm, T* y, int64_t rows, int n, int 
     if (blocks < 1) blocks = 1;
     if (n == 128) hipLaunchKernelGGL((fq_rowmm_kernel<128, T>), dim3((unsigned)blocks), dim3(256), 0, stream, x, Tm, y, rows);
     else if (n == 64) hipLaunchKernelGGL((fq_rowmm_kernel<64, T>), dim3((unsigned)blocks), dim3(256), 0, stream, x, Tm, y, rows);
-    else return -1000;
+    else return FQ_LAUNCH_NO_KERNEL;
     return (int)hipGetLastError();
 }
 int fq_launch_rowmm(int bf16_dtype, const void* x, const void* Tm, void* y, int64_t rows, int n, int n_cu, hipStream_t stream) {
@@ -406,7 +405,7 @@ int fq_launch_rowmm(int bf16_dtype, const void* x, const void* Tm, void* y, int6
 
 int fq_launch_kv_dequant(const uint8_t* q, const f16* param, int64_t rows, int hd, bool lac, f16* y, int n_cu,
                          hipStream_t stream) {
-    if (hd & 7) return -1000;
+    if (hd & 7) return FQ_LAUNCH_NO_KERNEL;
     int64_t blocks = (rows * (hd >> 3) + 255) / 256;
     if (blocks > (int64_t)n_cu * 8) blocks = (int64_t)n_cu * 8;
     if (blocks < 1) blocks = 1;

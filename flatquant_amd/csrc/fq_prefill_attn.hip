@@ -25,6 +25,7 @@
 // late (long) blocks are scheduled first, and where the unit count allows it the q_group heads of a KV head run back to back on one XCD
 // (workgroup ids are dealt round-robin over the 8 XCDs): the expectation, not measured, is that their K / V tiles then meet in that XCD's L2.
 #include "fq_kv_common.hpp"
+#include "fq_launch.hpp"
 
 namespace {
 
@@ -268,10 +269,10 @@ __global__ __launch_bounds__(PA_THREADS, 2) void fq_prefill_attn_kernel(PaArgs a
 
 int fq_launch_prefill_attn(f16* o, const f16* q, const f16* qt, const f16* k, const f16* v, const int* seq_start, const int* seq_len, int batch,
                            int seq, int q_heads, int kv_heads, hipStream_t stream) {
-    if (batch < 1 || seq < 1 || kv_heads < 1 || q_heads < 1 || q_heads % kv_heads) return -1000;
+    if (batch < 1 || seq < 1 || kv_heads < 1 || q_heads < 1 || q_heads % kv_heads) return FQ_LAUNCH_NO_KERNEL;
     const int nblk = (seq + PA_QB - 1) / PA_QB;
     const int64_t units = (int64_t)batch * nblk * kv_heads, wgs = units * (q_heads / kv_heads);
-    if (wgs > 0x7FFFFFFF) return -1000;
+    if (wgs > 0x7FFFFFFF) return FQ_LAUNCH_NO_KERNEL;
     PaArgs a = {o, q, qt, k, v, seq_start, seq_len, batch, seq, q_heads, kv_heads, nblk, units % 8 == 0 ? 1 : 0};
     if (qt != nullptr) {
         FQ_RAISE_LDS_CAP((fq_prefill_attn_kernel<true>), PA_LDS);

@@ -8,6 +8,7 @@
 //   fq_sym_quant_kernel     deploy/kernels/quant.cu:13-47  (fp16 division, rn, clamp, low nibble first)
 //   fq_sym_dequant_kernel   deploy/kernels/quant.cu:66-85
 #include "fq_common.hpp"
+#include "fq_launch.hpp"
 
 namespace {
 
@@ -350,7 +351,7 @@ int launch_rowquant(const T* x, int64_t rows, int cols, const FqQuantOut& out, i
     }
     FQ_RQ(2) FQ_RQ(4) FQ_RQ(8) FQ_RQ(RQ_MAXCH)
 #undef FQ_RQ
-    return -1000;
+    return FQ_LAUNCH_NO_KERNEL;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -505,7 +506,7 @@ static int launch_rowquant_any(int flags, const T* x, int64_t rows, int cols, co
     case (F) | FQ_QUANT_F16:                                                    \
         return launch_rowquant<(F) | FQ_QUANT_F16, T>(x, rows, cols, out, n_cu, stream);
     if (flags & FQ_ASYM) {  // (fq_capi admits it with FQ_OUT_FAKEQUANT alone)
-        if ((flags & (FQ_OUT_PACKED | FQ_OUT_FAKEQUANT | FQ_OUT_TRANSFORM)) != FQ_OUT_FAKEQUANT) return -1000;
+        if ((flags & (FQ_OUT_PACKED | FQ_OUT_FAKEQUANT | FQ_OUT_TRANSFORM)) != FQ_OUT_FAKEQUANT) return FQ_LAUNCH_NO_KERNEL;
         return (flags & FQ_QUANT_F16) ? launch_rowquant_asym<true, T>(x, rows, cols, out, n_cu, stream)
                                       : launch_rowquant_asym<false, T>(x, rows, cols, out, n_cu, stream);
     }
@@ -514,7 +515,7 @@ static int launch_rowquant_any(int flags, const T* x, int64_t rows, int cols, co
         FQ_CASE(FQ_OUT_FAKEQUANT)
         FQ_CASE(FQ_OUT_PACKED | FQ_OUT_FAKEQUANT)
         default:
-            return -1000;
+            return FQ_LAUNCH_NO_KERNEL;
     }
 #undef FQ_CASE
 }
@@ -569,7 +570,7 @@ __global__ __launch_bounds__(256) void fq_silu_mul_kernel(const f16* __restrict_
 }
 
 int fq_launch_silu_mul(const f16* gate, const f16* up, f16* y, int64_t n, int n_cu, hipStream_t stream) {
-    if (n & 7) return -1000;
+    if (n & 7) return FQ_LAUNCH_NO_KERNEL;
     const int64_t chunks = n >> 3;
     int64_t blocks = (chunks + 255) / 256;
     if (blocks > (int64_t)n_cu * 16) blocks = (int64_t)n_cu * 16;
@@ -578,7 +579,7 @@ int fq_launch_silu_mul(const f16* gate, const f16* up, f16* y, int64_t n, int n_
 }
 
 int fq_launch_rmsnorm(const f16* x, f16* y, int64_t rows, int cols, float eps, int n_cu, hipStream_t stream) {
-    if ((cols & 7) || cols < 8 || cols > 16384) return -1000;
+    if ((cols & 7) || cols < 8 || cols > 16384) return FQ_LAUNCH_NO_KERNEL;
     const int nchw = ((cols >> 3) + 63) / 64;
     int64_t wb = (rows + 3) / 4;
     if (wb > (int64_t)n_cu * 8) wb = (int64_t)n_cu * 8;
@@ -590,7 +591,7 @@ int fq_launch_rmsnorm(const f16* x, f16* y, int64_t rows, int cols, float eps, i
     }
     FQ_RN(4) FQ_RN(8) FQ_RN(16) FQ_RN(32)
 #undef FQ_RN
-    return -1000;
+    return FQ_LAUNCH_NO_KERNEL;
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -7,6 +7,7 @@
 // equal, frequency scaling is the caller's). A streaming kernel: a thread owns eight features j .. j + 7 of one (token, head) row AND their
 // partners at + hd / 2 — six 16-byte loads, two 16-byte stores, no traffic between lanes — so an output may be its own input.
 #include "fq_kv_common.hpp"
+#include "fq_launch.hpp"
 
 namespace {
 
@@ -41,9 +42,9 @@ __global__ __launch_bounds__(256) void fq_rope_kernel(f16* q_out, f16* k_out, co
 // q_heads / k_heads: 0 for a tensor that is not there (its pointers are then never read)
 int fq_launch_rope(f16* q_out, f16* k_out, const f16* q, const f16* k, const f16* cos, const f16* sin, int64_t tokens, int q_heads, int k_heads,
                    int head_dim, hipStream_t stream) {
-    if ((head_dim != 64 && head_dim != 128) || q_heads + k_heads < 1) return -1000;
+    if ((head_dim != 64 && head_dim != 128) || q_heads + k_heads < 1) return FQ_LAUNCH_NO_KERNEL;
     if (tokens <= 0) return 0;
-    if (tokens > 0x7FFFFFFF) return -1000;
+    if (tokens > 0x7FFFFFFF) return FQ_LAUNCH_NO_KERNEL;
     const dim3 grid((unsigned)tokens, (unsigned)(((q_heads + k_heads) * (head_dim / 16) + 255) / 256));
     if (head_dim == 128)
         hipLaunchKernelGGL(fq_rope_kernel<128>, grid, dim3(256), 0, stream, q_out, k_out, q, k, cos, sin, q_heads, k_heads);

@@ -1812,6 +1812,49 @@ def _kv_split_workspace(key, nbytes: int, device) -> Optional[torch.Tensor]:
     return ws
 
 
+def _kv_attn_front(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, q_trans, transpose_out, tokens_dim: bool, kv_copies: int = 1,
+                   append: bool = False, k_new=None, v_new=None):
+    """What the attention wrappers over the paged cache do before they launch: the tensor checks, the cache geometry, the index tensors, q's
+    shape ([batch, heads, head_dim]; with ``tokens_dim`` [batch, q_len, heads, head_dim]), the ``kv_copies`` and ``q_trans`` rules and the
+    output (q's shape, its last two dimensions swapped with ``transpose_out``). ``append``: ``k_new`` / ``v_new`` are the new row of
+    kv_decode_append (INT4 pages only), checked along.
+    -> (o, q's device, layers, cache heads, page_size, head_dim, batch, query heads, q_group = query heads per cache head, share = query
+    heads that read one set of rows, 1 if the pages are fp16, the five cache pointers as the entry points take them).
+    Every tensor attribute is read once: these wrappers are the host side of a 15 us call."""
+    _chk(q, "q")
+    cache_dtype = kv_data.dtype
+    if append:
+        _chk(k_new, "k_new"), _chk(v_new, "v_new"), _chk(kv_data, "kv_data", torch.uint8)
+    else:
+        _chk(kv_data, "kv_data", cache_dtype)
+    _chk(kv_param, "kv_param")
+    n_layers, kv_heads, page_size, hd = _kv_geometry(kv_data)
+    batch = _chk_kv_index(kv_indptr, kv_indices, last_page_offset)
+    shape = q.shape
+    if tokens_dim:
+        if len(shape) != 4 or shape[0] != batch or shape[3] != hd or shape[1] < 1 or shape[2] % kv_heads:
+            raise ValueError(f"q must be [{batch}, q_len >= 1, a multiple of {kv_heads}, {hd}]")
+    elif len(shape) != 3 or shape[0] != batch or shape[2] != hd or shape[1] % kv_heads:
+        # (round 6) a cache that holds the KV heads once: q carries q_group query heads per cache head (fq_kv_batch_decode_gqa)
+        raise ValueError(f"q must be [{batch}, a multiple of {kv_heads}, {hd}]")
+    if append and (k_new.shape != v_new.shape or k_new.dim() != 3 or k_new.shape[0] != batch or k_new.shape[2] != hd
+                   or kv_heads % k_new.shape[1]):
+        raise ValueError(f"k_new / v_new must be [{batch}, a divisor of {kv_heads}, {hd}]")
+    heads = shape[-2]
+    q_group = heads // kv_heads
+    if kv_copies > 1 and (q_group != 1 or kv_heads % kv_copies or kv_copies > 8):
+        raise ValueError(f"kv_copies={kv_copies}: needs a replicated cache (query heads == cache heads == {kv_heads}) in groups of at most 8")
+    if q_trans is not None:
+        _chk(q_trans, "q_trans")
+        if q_trans.shape != (hd, hd):
+            raise ValueError("q_trans must be [head_dim, head_dim]")
+    dev = q.device
+    o = torch.empty(shape[:-2] + (hd, heads) if transpose_out else shape, dtype=torch.float16, device=dev)
+    return (o, dev, n_layers, kv_heads, page_size, hd, batch, heads, q_group, kv_copies if kv_copies > 1 else q_group,
+            1 if cache_dtype == torch.float16 else 0,
+            (kv_data.data_ptr(), kv_param.data_ptr(), kv_indptr.data_ptr(), kv_indices.data_ptr(), last_page_offset.data_ptr()))
+
+
 def kv_batch_decode(q: torch.Tensor, kv_data: torch.Tensor, kv_param: torch.Tensor, kv_indptr: torch.Tensor,
                     kv_indices: torch.Tensor, last_page_offset: torch.Tensor, layer_idx: int,
                     q_trans: Optional[torch.Tensor] = None, transpose_out: bool = False, seq_hint: int = 0, split: bool = True,
@@ -1824,57 +1867,30 @@ def kv_batch_decode(q: torch.Tensor, kv_data: torch.Tensor, kv_param: torch.Tens
     REPLICATED layout whose g consecutive heads per KV head hold identical rows (kv_cache.py:286-296; the appends of this package write them so)
     and the launch reads one copy per group (fq_kv_batch_decode_copies): the same values from 1 / g of the bytes (the same output bit for bit
     below 32 (request, KV head) pairs; from there one workgroup serves a group: another order of the fp32 additions, as with split launches)."""
-    _chk(q, "q"), _chk(kv_data, "kv_data", kv_data.dtype), _chk(kv_param, "kv_param")
-    n_layers, kv_heads, page_size, hd = _kv_geometry(kv_data)
-    batch = _chk_kv_index(kv_indptr, kv_indices, last_page_offset)
-    f16_cache = kv_data.dtype == torch.float16
-    # (round 6) a cache that holds the KV heads once: q carries q_group query heads per cache head (fq_kv_batch_decode_gqa)
-    if q.dim() != 3 or q.shape[0] != batch or q.shape[2] != hd or q.shape[1] % kv_heads:
-        raise ValueError(f"q must be [{batch}, a multiple of {kv_heads}, {hd}]")
-    heads = q.shape[1]
-    q_group = heads // kv_heads
-    if kv_copies > 1 and (q_group != 1 or kv_heads % kv_copies or kv_copies > 8):
-        raise ValueError(f"kv_copies={kv_copies}: needs a replicated cache (query heads == cache heads == {kv_heads}) in groups of at most 8")
-    if q_trans is not None:
-        _chk(q_trans, "q_trans")
-        if q_trans.shape != (hd, hd):
-            raise ValueError("q_trans must be [head_dim, head_dim]")
-    o = torch.empty((batch, hd, heads) if transpose_out else (batch, heads, hd), dtype=torch.float16, device=q.device)
+    o, dev, n_layers, kv_heads, page_size, hd, batch, heads, q_group, share, f16_cache, cache = _kv_attn_front(
+        q, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, q_trans, transpose_out, False, kv_copies)
     if batch == 0:
         return o
-    with _on(q.device):
-        if kv_copies > 1:
-            nbytes = int(lib.fq_kv_decode_workspace_bytes_gqa(batch, heads // kv_copies, kv_copies, hd)) if split else 0
-            stream = _stream(q)
-            ws = _kv_split_workspace((q.device.index, stream.value, batch * heads, hd), nbytes, q.device) if nbytes > 0 else None
-            check(lib.fq_kv_batch_decode_copies(1 if f16_cache else 0, _ptr(o), _ptr(q), _ptr(q_trans), 1 if transpose_out else 0, _ptr(kv_data),
-                                                _ptr(kv_param), _ptr(kv_indptr), _ptr(kv_indices), _ptr(last_page_offset),
-                                                n_layers, layer_idx, heads, kv_copies, page_size, hd, batch, int(seq_hint), _ptr(ws),
-                                                nbytes if ws is not None else 0, stream))
-            return o
+    with _on(dev):
         if not split:
             nbytes = 0
-        elif q_group > 1:
-            nbytes = int(lib.fq_kv_decode_workspace_bytes_gqa(batch, kv_heads, q_group, hd))
+        elif share > 1:
+            nbytes = int(lib.fq_kv_decode_workspace_bytes_gqa(batch, heads // share, share, hd))
         else:
             nbytes = int(lib.fq_kv_decode_workspace_bytes(batch, heads, hd))
-        stream = _stream(q)
-        ws = _kv_split_workspace((q.device.index, stream.value, batch * heads, hd), nbytes, q.device) if nbytes > 0 else None
-        if q_group > 1:
-            check(lib.fq_kv_batch_decode_gqa(1 if f16_cache else 0, _ptr(o), _ptr(q), _ptr(q_trans), 1 if transpose_out else 0, _ptr(kv_data),
-                                             _ptr(kv_param), _ptr(kv_indptr), _ptr(kv_indices), _ptr(last_page_offset),
-                                             n_layers, layer_idx, kv_heads, q_group, page_size, hd, batch, int(seq_hint), _ptr(ws),
-                                             nbytes if ws is not None else 0, stream))
-            return o
-        if ws is not None:
-            check(lib.fq_kv_batch_decode_split(1 if f16_cache else 0, _ptr(o), _ptr(q), _ptr(q_trans), 1 if transpose_out else 0, _ptr(kv_data),
-                                               _ptr(kv_param), _ptr(kv_indptr), _ptr(kv_indices), _ptr(last_page_offset),
-                                               n_layers, layer_idx, heads, page_size, hd, batch, int(seq_hint), _ptr(ws), nbytes, stream))
-            return o
-        decode = lib.fq_kv_batch_decode_f16_ex if f16_cache else lib.fq_kv_batch_decode_i4_ex
-        check(decode(_ptr(o), _ptr(q), _ptr(q_trans), 1 if transpose_out else 0, _ptr(kv_data),
-                     _ptr(kv_param), _ptr(kv_indptr), _ptr(kv_indices), _ptr(last_page_offset),
-                     n_layers, layer_idx, heads, page_size, hd, batch, _stream(q)))
+        stream = ctypes.c_void_p(_stream_handle(dev))
+        ws = _kv_split_workspace((dev.index, stream.value, batch * heads, hd), nbytes, dev) if nbytes > 0 else None
+        tail = (int(seq_hint), _ptr(ws), nbytes if ws is not None else 0, stream)
+        if kv_copies > 1:
+            entry, lead, group = lib.fq_kv_batch_decode_copies, (f16_cache,), (heads, kv_copies)
+        elif q_group > 1:
+            entry, lead, group = lib.fq_kv_batch_decode_gqa, (f16_cache,), (kv_heads, q_group)
+        elif ws is not None:
+            entry, lead, group = lib.fq_kv_batch_decode_split, (f16_cache,), (heads,)
+        else:
+            entry, lead, group, tail = lib.fq_kv_batch_decode_f16_ex if f16_cache else lib.fq_kv_batch_decode_i4_ex, (), (heads,), (stream,)
+        check(entry(*lead, o.data_ptr(), q.data_ptr(), _ptr(q_trans), 1 if transpose_out else 0, *cache, n_layers, layer_idx, *group, page_size, hd,
+                    batch, *tail))
     return o
 
 
@@ -1887,32 +1903,17 @@ def kv_batch_extend(q: torch.Tensor, kv_data: torch.Tensor, kv_param: torch.Tens
     attends rows 0 .. length - T + t. Heads, ``q_trans``, ``seq_hint``, ``split`` and ``kv_copies`` as kv_batch_decode: heads = cache heads
     x q_group (a cache that holds the KV heads once) or, with ``kv_copies`` = g > 1, the replicated layout read one copy per group.
     head_dim 128."""
-    _chk(q, "q"), _chk(kv_data, "kv_data", kv_data.dtype), _chk(kv_param, "kv_param")
-    n_layers, kv_heads, page_size, hd = _kv_geometry(kv_data)
-    batch = _chk_kv_index(kv_indptr, kv_indices, last_page_offset)
-    f16_cache = kv_data.dtype == torch.float16
-    if q.dim() != 4 or q.shape[0] != batch or q.shape[3] != hd or q.shape[1] < 1 or q.shape[2] % kv_heads:
-        raise ValueError(f"q must be [{batch}, q_len >= 1, a multiple of {kv_heads}, {hd}]")
-    q_len, heads = q.shape[1], q.shape[2]
-    q_group = heads // kv_heads
-    if kv_copies > 1:
-        if q_group != 1 or kv_heads % kv_copies or kv_copies > 8:
-            raise ValueError(f"kv_copies={kv_copies}: needs a replicated cache (query heads == cache heads == {kv_heads}) in groups of at most 8")
-        q_group = kv_copies
-    if q_trans is not None:
-        _chk(q_trans, "q_trans")
-        if q_trans.shape != (hd, hd):
-            raise ValueError("q_trans must be [head_dim, head_dim]")
-    o = torch.empty((batch, q_len, hd, heads) if transpose_out else (batch, q_len, heads, hd), dtype=torch.float16, device=q.device)
+    o, dev, n_layers, kv_heads, page_size, hd, batch, heads, _, share, f16_cache, cache = _kv_attn_front(
+        q, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, q_trans, transpose_out, True, kv_copies)
+    q_len = q.shape[1]
     if batch == 0:
         return o
-    with _on(q.device):
+    with _on(dev):
         nbytes = int(lib.fq_kv_extend_workspace_bytes(batch, heads, q_len, hd)) if split else 0
-        stream = _stream(q)
-        ws = _kv_split_workspace(("extend", q.device.index, stream.value, batch, heads, q_len, hd), nbytes, q.device) if nbytes > 0 else None
-        check(lib.fq_kv_batch_extend(1 if f16_cache else 0, _ptr(o), _ptr(q), _ptr(q_trans), 1 if transpose_out else 0, _ptr(kv_data),
-                                     _ptr(kv_param), _ptr(kv_indptr), _ptr(kv_indices), _ptr(last_page_offset), n_layers, layer_idx,
-                                     kv_heads, q_group, kv_copies, q_len, page_size, hd, batch, int(seq_hint), _ptr(ws),
+        stream = ctypes.c_void_p(_stream_handle(dev))
+        ws = _kv_split_workspace(("extend", dev.index, stream.value, batch, heads, q_len, hd), nbytes, dev) if nbytes > 0 else None
+        check(lib.fq_kv_batch_extend(f16_cache, o.data_ptr(), q.data_ptr(), _ptr(q_trans), 1 if transpose_out else 0, *cache, n_layers, layer_idx,
+                                     kv_heads, share, kv_copies, q_len, page_size, hd, batch, int(seq_hint), _ptr(ws),
                                      nbytes if ws is not None else 0, stream))
     return o
 
@@ -1925,29 +1926,13 @@ def kv_chunk_extend(q: torch.Tensor, kv_data: torch.Tensor, kv_param: torch.Tens
     128 (token, head) rows of q), every 64-row tile of the cache unpacked once for all of them. No workspace and no split: two calls are
     bit-identical, and a step fed as two consecutive calls equals the one call bit for bit. head_dim 128; 1, 2, 4 or 8 query heads per set of
     cached rows (anything else: FqError, kv_batch_extend takes it)."""
-    _chk(q, "q"), _chk(kv_data, "kv_data", kv_data.dtype), _chk(kv_param, "kv_param")
-    n_layers, kv_heads, page_size, hd = _kv_geometry(kv_data)
-    batch = _chk_kv_index(kv_indptr, kv_indices, last_page_offset)
-    f16_cache = kv_data.dtype == torch.float16
-    if q.dim() != 4 or q.shape[0] != batch or q.shape[3] != hd or q.shape[1] < 1 or q.shape[2] % kv_heads:
-        raise ValueError(f"q must be [{batch}, q_len >= 1, a multiple of {kv_heads}, {hd}]")
-    q_len, heads = q.shape[1], q.shape[2]
-    q_group = heads // kv_heads
-    if kv_copies > 1:
-        if q_group != 1 or kv_heads % kv_copies or kv_copies > 8:
-            raise ValueError(f"kv_copies={kv_copies}: needs a replicated cache (query heads == cache heads == {kv_heads}) in groups of at most 8")
-        q_group = kv_copies
-    if q_trans is not None:
-        _chk(q_trans, "q_trans")
-        if q_trans.shape != (hd, hd):
-            raise ValueError("q_trans must be [head_dim, head_dim]")
-    o = torch.empty((batch, q_len, hd, heads) if transpose_out else (batch, q_len, heads, hd), dtype=torch.float16, device=q.device)
+    o, dev, n_layers, kv_heads, page_size, hd, batch, _, _, share, f16_cache, cache = _kv_attn_front(
+        q, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, q_trans, transpose_out, True, kv_copies)
     if batch == 0:
         return o
-    with _on(q.device):
-        check(lib.fq_kv_chunk_extend(1 if f16_cache else 0, _ptr(o), _ptr(q), _ptr(q_trans), 1 if transpose_out else 0, _ptr(kv_data),
-                                     _ptr(kv_param), _ptr(kv_indptr), _ptr(kv_indices), _ptr(last_page_offset), n_layers, layer_idx,
-                                     kv_heads, q_group, kv_copies, q_len, page_size, hd, batch, _stream(q)))
+    with _on(dev):
+        check(lib.fq_kv_chunk_extend(f16_cache, o.data_ptr(), q.data_ptr(), _ptr(q_trans), 1 if transpose_out else 0, *cache, n_layers, layer_idx,
+                                     kv_heads, share, kv_copies, q.shape[1], page_size, hd, batch, ctypes.c_void_p(_stream_handle(dev))))
     return o
 
 
@@ -2071,19 +2056,9 @@ def kv_decode_append(q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, 
     ``kv_decode_append(hadamard(q), hadamard(k_new), v_new, None, ...)``. It excludes ``trans``, ``q_trans`` and ``rope`` (ValueError)."""
     if had and (trans is not None or q_trans is not None or rope is not None):
         raise ValueError("kv_decode_append(had=True): the launch's own Hadamard rotation excludes trans, q_trans and rope")
-    _chk(q, "q"), _chk(k_new, "k_new"), _chk(v_new, "v_new"), _chk(kv_data, "kv_data", torch.uint8), _chk(kv_param, "kv_param")
-    n_layers, cache_heads, page_size, hd = _kv_geometry(kv_data)
-    batch = _chk_kv_index(kv_indptr, kv_indices, last_page_offset)
-    if q.dim() != 3 or q.shape[0] != batch or q.shape[2] != hd or q.shape[1] % cache_heads:
-        raise ValueError(f"q must be [{batch}, a multiple of {cache_heads}, {hd}]")
-    if k_new.shape != v_new.shape or k_new.dim() != 3 or k_new.shape[0] != batch or k_new.shape[2] != hd or cache_heads % k_new.shape[1]:
-        raise ValueError(f"k_new / v_new must be [{batch}, a divisor of {cache_heads}, {hd}]")
-    heads, src_heads = q.shape[1], k_new.shape[1]
-    q_group = heads // cache_heads
-    if q_trans is not None:
-        _chk(q_trans, "q_trans")
-        if q_trans.shape != (hd, hd):
-            raise ValueError("q_trans must be [head_dim, head_dim]")
+    o, dev, n_layers, cache_heads, page_size, hd, batch, heads, q_group, _, _, cache = _kv_attn_front(
+        q, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, q_trans, transpose_out, False, 1, True, k_new, v_new)
+    src_heads = k_new.shape[1]
     cos = sin = None
     if rope is not None:
         cos, sin = rope
@@ -2091,18 +2066,16 @@ def kv_decode_append(q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, 
         if cos.numel() != batch * hd or sin.numel() != batch * hd or cos.shape[-1] != hd or sin.shape[-1] != hd:
             raise ValueError(f"rope = (cos, sin) must each be [{batch}, {hd}] (the step's row of the tables per request)")
     img = kv_transform_image(trans) if trans is not None else None
-    o = torch.empty((batch, hd, heads) if transpose_out else (batch, heads, hd), dtype=torch.float16, device=q.device)
     if batch == 0:
         return o
-    with _on(q.device):
+    with _on(dev):
         one = bool(read_one_copy) and q_group == 1 and cache_heads // src_heads > 1
         share = cache_heads // src_heads if one else q_group           # query heads that share one set of rows
         nbytes = int(lib.fq_kv_decode_workspace_bytes_gqa(batch, heads // share, share, hd)) if split else 0
-        stream = _stream(q)
-        ws = _kv_split_workspace((q.device.index, stream.value, batch * heads, hd), nbytes, q.device) if nbytes > 0 else None
-        args = (_ptr(o), _ptr(q), _ptr(q_trans), 1 if transpose_out else 0, _ptr(k_new), _ptr(v_new), _ptr(img), src_heads,
-                _ptr(kv_data), _ptr(kv_param), _ptr(kv_indptr), _ptr(kv_indices), _ptr(last_page_offset),
-                n_layers, layer_idx, cache_heads, q_group, page_size, hd, batch, int(seq_hint), 1 if one else 0, _ptr(ws),
+        stream = ctypes.c_void_p(_stream_handle(dev))
+        ws = _kv_split_workspace((dev.index, stream.value, batch * heads, hd), nbytes, dev) if nbytes > 0 else None
+        args = (o.data_ptr(), q.data_ptr(), _ptr(q_trans), 1 if transpose_out else 0, k_new.data_ptr(), v_new.data_ptr(), _ptr(img), src_heads,
+                *cache, n_layers, layer_idx, cache_heads, q_group, page_size, hd, batch, int(seq_hint), 1 if one else 0, _ptr(ws),
                 nbytes if ws is not None else 0, stream)
         if had:
             had_scale = float(1.0 / torch.tensor(hd).sqrt())  # the fp32 value ops.hadamard passes for rows of head_dim
