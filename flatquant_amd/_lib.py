@@ -137,6 +137,7 @@ SYMBOLS = {
     "fq_rowquant_f16": (_i, [_vp, _i64, _i, _fp, _fp, _i, _i, _vpp, _vpp, _vpp, _vp]),
     "fq_sym_quant_f16": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
     "fq_sym_dequant_i32_f16": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp]),
+    "fq_debug_kron_route": (_i, [_i, _i, _i, _i64, _i, _i, _i, _i, _i, _f, _i64, ctypes.c_char_p, _i]),
     "fq_last_error": (ctypes.c_char_p, []),
     "fq_version": (_i, []),
 }
@@ -167,6 +168,14 @@ def _load() -> ctypes.CDLL:
 
 
 lib = _load()
+
+
+def kron_route(M, N, flags, *, rows=1, bf16=False, form=0, n_clips=1, diag=False, in2=False, post_scale=1.0, workspace_bytes=1 << 30):
+    """the kernel a Kronecker launch runs, "fq_kron_tiles_kernel<3,4,128,3,6,0,f16,0>", or the launcher code as text (fq_debug_kron_route)"""
+    buf = ctypes.create_string_buffer(128)
+    n = lib.fq_debug_kron_route(int(bf16), form, flags, rows, M, N, n_clips, int(diag), int(in2), post_scale, workspace_bytes, buf, len(buf))
+    assert n > 0
+    return buf.value.decode()
 
 
 def check(code: int) -> None:

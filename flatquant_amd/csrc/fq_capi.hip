@@ -111,8 +111,9 @@ static int kron_dispatch(const char* what, const FqQuantOut& o, int flags, const
                                        ((flags & (FQ_QUANT_F16 | FQ_OUT_FAKEQUANT | FQ_OUT_TRANSFORM)) && !(flags & FQ_ROUND_Y_F16))))
         return fail(FQ_EUNSUPPORTED, "%s: FQ_GROUP128 needs one clip set, M*N %% 128 == 0, and FQ_ROUND_Y_F16 for any output set other "
                     "than packed with fp32 arithmetic", what);
+    const FqKronRoute r = fq_kron_route(flags, rows, M, N, diag != nullptr, o, workspace ? workspace_bytes : 0, true, fq_kron_measure_mask());
     if (M == 64 && N == 64) {
-        // the workspace is OPTIONAL at 64 x 64: with one (>= 16 KB) the kernel reads the fragment image from it (written here
+        // the workspace is OPTIONAL at 64 x 64: with one (>= 32 KB) the kernel reads the fragment image from it (written here
         // unless FQ_WS_PREPARED says it is there already), without one it gathers the fragments from the matrices itself
         const void* prep = (workspace && workspace_bytes >= FQ_K64_WS_BYTES) ? workspace : nullptr;
         if (prep && !(flags & FQ_WS_PREPARED)) {
@@ -122,21 +123,19 @@ static int kron_dispatch(const char* what, const FqQuantOut& o, int flags, const
             if (rc != 0) return check_launch(rc, what);
             flags |= FQ_WS_PREPARED;   // (both images are there now, also for the fall-through below)
         }
-        rc = fq_launch_kron64(flags & ~FQ_WS_PREPARED, (const f16*)x, (const f16*)left, (const f16*)right, (const f16*)diag,
-                              rows, o, n_cu, (hipStream_t)stream, prep);
-        if (rc != FQ_LAUNCH_NO_KERNEL) return check_launch(rc, what);
+        if (r.rc == 0 && r.family == FQ_KF_K64)
+            return check_launch(fq_launch_kron64(r.t[0], dt, x, left, right, diag, rows, o, n_cu, (hipStream_t)stream, prep), what);
         if (dt) return fail(FQ_EUNSUPPORTED, "%s: output set 0x%x has no bf16 kernel at 64 x 64", what, flags & ~dt);
         if ((o.rt_flags & FQ_GROUP128) && !(flags & FQ_ROUND_Y_F16))
             return fail(FQ_EUNSUPPORTED, "%s: FQ_GROUP128 at 64 x 64 needs the packed-only output set or FQ_ROUND_Y_F16", what);
-        if (prep) {   // the second half of the 64 x 64 workspace is the other kernel family's image
-            workspace = static_cast<unsigned char*>(workspace) + FQ_K64_IMAGE_BYTES;
+        if (prep) {   // the second half of the 64 x 64 workspace is the other kernel family's image (r.ws_skip)
             workspace_bytes -= FQ_K64_IMAGE_BYTES;
         } else {
             flags &= ~FQ_WS_PREPARED;
         }
     }
-    rc = fq_launch_kron_generic(flags, (const f16*)x, (const f16*)left, (const f16*)right, (const f16*)diag,
-                                rows, M, N, o, workspace, workspace_bytes, n_cu, (hipStream_t)stream);
+    rc = fq_launch_kron(r, flags, (const f16*)x, (const f16*)left, (const f16*)right, (const f16*)diag, rows, M, N, o, workspace, n_cu,
+                        (hipStream_t)stream);
     if (rc == FQ_LAUNCH_NEED_WS)
         return fail(FQ_EINVAL, "%s: workspace of %lld bytes required for M=%d N=%d (got %lld)", what,
                     (long long)fq_kron_generic_workspace_bytes(M, N), M, N, (long long)(workspace ? workspace_bytes : 0));
@@ -323,8 +322,8 @@ int fq_rmsnorm_kron_quant_f16(const void* x, float eps, const void* left, const 
     if (!x || !left || !right) return fail(FQ_EINVAL, "fq_rmsnorm_kron_quant_f16: x/left/right is NULL");
     FQ_NEED_ALIGN16("fq_rmsnorm_kron_quant_f16", x, left, right);
     o.rms_eps = eps;
-    rc = fq_launch_kron64(flags | FQ_IN_RMSNORM, (const f16*)x, (const f16*)left, (const f16*)right, nullptr, rows, o,
-                          cu_count(), (hipStream_t)stream);
+    rc = fq_launch_kron64(fq_kron64_inst(flags | FQ_IN_RMSNORM, o.rt_flags, false), 0, x, left, right, nullptr, rows, o, cu_count(),
+                          (hipStream_t)stream);
     if (rc == FQ_LAUNCH_NO_KERNEL) return fail(FQ_EUNSUPPORTED, "fq_rmsnorm_kron_quant_f16: output set 0x%x has no fused kernel", flags);
     return check_launch(rc, "fq_rmsnorm_kron_quant_f16");
 }
@@ -1474,6 +1473,30 @@ int fq_sym_dequant_i32_f16(const void* q, const void* scale_row, const void* sca
 }
 
 /* debug only (not declared in fqhip.h): per-phase cycle accounting of the d=4096 packed kernel */
+// Which kernel a Kronecker launch runs, as text (include/fqhip.h): the descriptors an entry point hands fq_kron_route, rebuilt from plain arguments.
+int fq_debug_kron_route(int bf16_dtype, int form, int flags, int64_t rows, int M, int N, int n_clips, int has_diag, int has_in2,
+                        float post_scale, int64_t workspace_bytes, char* buf, int buf_bytes) {
+    FqQuantOut o;
+    memset(&o, 0, sizeof(o));
+    static const f16 some = (f16)0.0f;   // (presence is all the route looks at)
+    f16* p = const_cast<f16*>(&some);
+    o.n_clips = (flags & (FQ_OUT_PACKED | FQ_OUT_FAKEQUANT)) ? n_clips : 0;
+    o.rt_flags = flags & (FQ_ROUND_Y_F16 | FQ_NO_CLAMP0 | FQ_GROUP128 | FQ_SIG_F16 | FQ_RATIO_POST);
+    if (flags & FQ_OUT_FAKEQUANT) o.fq[0] = p;
+    if (flags & FQ_OUT_TRANSFORM) o.y = p;
+    if (has_in2) o.in2 = p;
+    if (form == 3) o.post_scale = post_scale == 1.0f ? 0.0f : post_scale;
+    static const int64_t offsets[2] = {0, 0};
+    if (form == 4 && (flags & (FQ_OUT_PACKED | FQ_OUT_FAKEQUANT))) o.group_offsets = offsets;
+    const int in = form == 1 ? FQ_IN_RMSNORM : form == 2 ? FQ_IN_SILU_MUL : form == 3 ? (has_in2 ? FQ_IN_SILU_MUL : 0) | FQ_NO_WAVE_KERNEL : 0;
+    const bool k64 = M == 64 && N == 64;
+    const bool dispatch = form == 0 || form == 4 || (form == 1 && k64);   // (kron_dispatch: 64 x 64 goes to fq_kron64.hip first)
+    if (form == 1 && k64 && fq_kron64_inst(flags | in, o.rt_flags, false) < 0) return fq_kron_route_name(FqKronRoute{FQ_LAUNCH_NO_KERNEL}, buf, buf_bytes);
+    const FqKronRoute r = fq_kron_route((flags & ~FQ_WS_PREPARED) | in | (bf16_dtype ? FQ_DT_BF16 : 0), rows, M, N, has_diag != 0, o, workspace_bytes,
+                                        dispatch, fq_kron_measure_mask());
+    return fq_kron_route_name(r, buf, buf_bytes);
+}
+
 int fq_debug_kron64_trace(const void* x, const void* left, const void* right, int64_t rows, void* q, void* scale,
                           void* trace, void* stream) {
     FqQuantOut o;

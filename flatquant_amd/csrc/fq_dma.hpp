@@ -118,3 +118,39 @@ __device__ __forceinline__ void dma_span(const unsigned char* src, int n, unsign
             : "memory");
     }
 }
+
+// ---- token groups of one workgroup that meet without s_barrier (fq_kron_trio.hip, fq_kron_duo.hip, fq_kron_tiles.hip) ----
+#ifndef FQ_PRIO_MFMA
+#define FQ_PRIO_MFMA 2   // s_setprio level of a wave inside its GEMM phases (0: off)
+#endif
+
+// LDS control words are touched through explicit ds_* instructions: a generic-pointer access would be a FLAT operation,
+// whose s_waitcnt vmcnt(0) drains the DMA in flight.
+__device__ __forceinline__ unsigned fq_lds_read(unsigned addr) {
+    unsigned v;
+    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addr) : "memory");
+    return v;
+}
+__device__ __forceinline__ unsigned fq_lds_add_rtn(unsigned addr, unsigned val) {
+    unsigned v;
+    asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addr), "v"(val) : "memory");
+    return v;
+}
+__device__ __forceinline__ void fq_lds_write(unsigned addr, unsigned val) {
+    asm volatile("ds_write_b32 %0, %1" : : "v"(addr), "v"(val) : "memory");
+}
+
+// Group meeting on a counter in LDS: every wave adds one when it arrives (its own LDS traffic done) and spins until the
+// arrivals of this meeting are in (target: the count after them), SLEEP x 64 cycles between two polls. LDS operations of one wave
+// complete in order, so a wave that sees the count also sees what the others wrote before arriving.
+template <int SLEEP = 1>
+__device__ __forceinline__ void fq_meet(unsigned cnt_lds, unsigned target, int lane) {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (lane == 0) asm volatile("ds_add_u32 %0, %1" : : "v"(cnt_lds), "v"(1u) : "memory");
+    for (;;) {
+        unsigned v;
+        asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(cnt_lds) : "memory");
+        if ((unsigned)__builtin_amdgcn_readfirstlane((int)v) >= target) break;
+        __builtin_amdgcn_s_sleep(SLEEP);
+    }
+}

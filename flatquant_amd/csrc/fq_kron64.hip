@@ -35,8 +35,7 @@
 namespace {
 
 constexpr int KM = 64, KN = 64, KD = KM * KN;
-constexpr int FQ_K64_G128 = 0x10000;     // internal template bits (not ABI flags): the FQ_GROUP128 instantiation,
-constexpr int FQ_K64_GROUPED = 0x20000;  // the grouped-launch instantiations (fq_kron_quant_grouped_f16)
+// (FQ_K64_G128, FQ_K64_GROUPED: fq_kron_route.hpp)
 constexpr int FQ_K64_MULTI = 0x40000;    // (round 4) the multi-job instantiation (fq_kron_quant_multi_f16): ONE launch over several
                                          // independent (activations, factor pair, outputs) jobs — a layer each, a rank's shard each
 // One job of a multi-job launch, device memory, filled by the launcher (fq_capi.hip). Every job runs on `bpj` consecutive
@@ -1150,73 +1149,35 @@ int fq_launch_kron64_multi(int bf16_dtype, const void* jobs, int n_jobs, int bpj
                       : launch_kron64_multi<f16>((const FqKron64Job*)jobs, n_jobs, bpj, out, stream);
 }
 
-template <typename T>
-static int launch_kron64_any(int flags, const T* x, const T* left, const T* right, const T* diag,
-                             int64_t rows, const FqQuantOut& out, int n_cu, hipStream_t stream, const void* prep) {
-    // Compile-time specialisations: output set x fp16-quant arithmetic. Everything else is run-time.
-#define FQ_CASE(F)                                                                     \
-    case (F):                                                                          \
-        return launch_kron64<(F), T>(x, left, right, diag, rows, out, n_cu, stream, prep);      \
-    case (F) | FQ_QUANT_F16:                                                           \
-        return launch_kron64<(F) | FQ_QUANT_F16, T>(x, left, right, diag, rows, out, n_cu, stream, prep);
-    if (out.rt_flags & FQ_GROUP128) {  // per-128-element scales: packed output, fp32 quantiser arithmetic only
-        if ((flags & FQ_CT_MASK) != FQ_OUT_PACKED) return FQ_LAUNCH_NO_KERNEL;
-        if (out.group_offsets != nullptr)
-            return launch_kron64<FQ_OUT_PACKED | FQ_K64_G128 | FQ_K64_GROUPED, T>(x, left, right, diag, rows, out, n_cu, stream, prep);
-        return launch_kron64<FQ_OUT_PACKED | FQ_K64_G128, T>(x, left, right, diag, rows, out, n_cu, stream, prep);
-    }
-    if (out.group_offsets != nullptr) {  // grouped launch: packed or fake-quant output (+ the transform)
-        switch (flags & FQ_CT_MASK) {
-            case FQ_OUT_PACKED:
-                return launch_kron64<FQ_OUT_PACKED | FQ_K64_GROUPED, T>(x, left, right, diag, rows, out, n_cu, stream, prep);
-            case FQ_OUT_FAKEQUANT:
-                return launch_kron64<FQ_OUT_FAKEQUANT | FQ_K64_GROUPED, T>(x, left, right, diag, rows, out, n_cu, stream, prep);
-            case FQ_OUT_PACKED | FQ_OUT_TRANSFORM:
-                return launch_kron64<FQ_OUT_PACKED | FQ_OUT_TRANSFORM | FQ_K64_GROUPED, T>(x, left, right, diag, rows, out, n_cu, stream, prep);
-            case FQ_OUT_FAKEQUANT | FQ_OUT_TRANSFORM:
-                return launch_kron64<FQ_OUT_FAKEQUANT | FQ_OUT_TRANSFORM | FQ_K64_GROUPED, T>(x, left, right, diag, rows, out, n_cu, stream, prep);
-            // the all-low-precision quantiser (clip parameters of the activation's dtype: the DeepSeek flow under
-            // torch.set_default_dtype(bfloat16), main_dpskv3.py:395)
-            case FQ_OUT_FAKEQUANT | FQ_QUANT_F16:
-                return launch_kron64<FQ_OUT_FAKEQUANT | FQ_QUANT_F16 | FQ_K64_GROUPED, T>(x, left, right, diag, rows, out, n_cu, stream, prep);
-            case FQ_OUT_FAKEQUANT | FQ_OUT_TRANSFORM | FQ_QUANT_F16:
-                return launch_kron64<FQ_OUT_FAKEQUANT | FQ_OUT_TRANSFORM | FQ_QUANT_F16 | FQ_K64_GROUPED, T>(x, left, right, diag, rows, out, n_cu, stream, prep);
-            default:
-                return FQ_LAUNCH_NO_KERNEL;
-        }
-    }
-    switch (flags & FQ_CT_MASK) {
-        FQ_CASE(FQ_OUT_PACKED)
-        FQ_CASE(FQ_OUT_FAKEQUANT)
-        FQ_CASE(FQ_OUT_PACKED | FQ_OUT_FAKEQUANT)
-        FQ_CASE(FQ_OUT_TRANSFORM | FQ_OUT_PACKED)
-        FQ_CASE(FQ_OUT_TRANSFORM | FQ_OUT_FAKEQUANT)
-        FQ_CASE(FQ_OUT_TRANSFORM | FQ_OUT_PACKED | FQ_OUT_FAKEQUANT)
-        // (the RMSNorm-fused launches serve deploy.nn.RMSNorm, an fp16-only module in the reference)
-        case FQ_OUT_PACKED | FQ_IN_RMSNORM:
-            if constexpr (FqVec<T>::is_f16) return launch_kron64<FQ_OUT_PACKED | FQ_IN_RMSNORM, T>(x, left, right, diag, rows, out, n_cu, stream, prep);
-            return FQ_LAUNCH_NO_KERNEL;
-        case FQ_OUT_TRANSFORM | FQ_IN_RMSNORM:
-            if constexpr (FqVec<T>::is_f16) return launch_kron64<FQ_OUT_TRANSFORM | FQ_IN_RMSNORM, T>(x, left, right, diag, rows, out, n_cu, stream, prep);
-            return FQ_LAUNCH_NO_KERNEL;
-        case FQ_OUT_TRANSFORM | FQ_OUT_PACKED | FQ_IN_RMSNORM:
-            if constexpr (FqVec<T>::is_f16) return launch_kron64<FQ_OUT_TRANSFORM | FQ_OUT_PACKED | FQ_IN_RMSNORM, T>(x, left, right, diag, rows, out, n_cu, stream, prep);
-            return FQ_LAUNCH_NO_KERNEL;
-        case FQ_OUT_TRANSFORM:
-        case FQ_OUT_TRANSFORM | FQ_QUANT_F16:
-            return launch_kron64<FQ_OUT_TRANSFORM, T>(x, left, right, diag, rows, out, n_cu, stream, prep);
-        default:
-            return FQ_LAUNCH_NO_KERNEL;
-    }
-#undef FQ_CASE
-}
+// fq_kron64_kernel<FLAGS, false, T>: the compile-time specialisations (output set x fp16-quant arithmetic, group-128, grouped, RMSNorm in
+// front: fq_kron64_inst, fq_kron_route.hip, names the one a launch runs). Everything else is run-time.
+#define FQ_K64_Q(X, F) X(F) X((F) | FQ_QUANT_F16)
+#define FQ_K64_LIST(X)                                                                                                              \
+    X(FQ_OUT_PACKED | FQ_K64_G128 | FQ_K64_GROUPED) X(FQ_OUT_PACKED | FQ_K64_G128)                                                  \
+    X(FQ_OUT_PACKED | FQ_K64_GROUPED) X(FQ_OUT_FAKEQUANT | FQ_K64_GROUPED) X(FQ_OUT_PACKED | FQ_OUT_TRANSFORM | FQ_K64_GROUPED)      \
+    X(FQ_OUT_FAKEQUANT | FQ_OUT_TRANSFORM | FQ_K64_GROUPED) X(FQ_OUT_FAKEQUANT | FQ_QUANT_F16 | FQ_K64_GROUPED)                     \
+    X(FQ_OUT_FAKEQUANT | FQ_OUT_TRANSFORM | FQ_QUANT_F16 | FQ_K64_GROUPED)                                                          \
+    FQ_K64_Q(X, FQ_OUT_PACKED) FQ_K64_Q(X, FQ_OUT_FAKEQUANT) FQ_K64_Q(X, FQ_OUT_PACKED | FQ_OUT_FAKEQUANT) FQ_K64_Q(X, FQ_OUT_TRANSFORM | FQ_OUT_PACKED)  \
+    FQ_K64_Q(X, FQ_OUT_TRANSFORM | FQ_OUT_FAKEQUANT) FQ_K64_Q(X, FQ_OUT_TRANSFORM | FQ_OUT_PACKED | FQ_OUT_FAKEQUANT) X(FQ_OUT_TRANSFORM)
+// ... and on f16 only (the RMSNorm-fused launches serve deploy.nn.RMSNorm, an fp16-only module in the reference)
+#define FQ_K64_RMS_LIST(X) X(FQ_OUT_PACKED | FQ_IN_RMSNORM) X(FQ_OUT_TRANSFORM | FQ_IN_RMSNORM) X(FQ_OUT_TRANSFORM | FQ_OUT_PACKED | FQ_IN_RMSNORM)
 
-int fq_launch_kron64(int flags, const f16* x, const f16* left, const f16* right, const f16* diag,
-                     int64_t rows, const FqQuantOut& out, int n_cu, hipStream_t stream, const void* prep) {
-    if (flags & FQ_DT_BF16)
-        return launch_kron64_any<bf16>(flags & ~FQ_DT_BF16, (const bf16*)x, (const bf16*)left, (const bf16*)right, (const bf16*)diag,
-                                       rows, out, n_cu, stream, prep);
-    return launch_kron64_any<f16>(flags, x, left, right, diag, rows, out, n_cu, stream, prep);
+int fq_launch_kron64(int k64_flags, int bf16_dtype, const void* x, const void* left, const void* right, const void* diag, int64_t rows,
+                     const FqQuantOut& out, int n_cu, hipStream_t stream, const void* prep) {
+#define X(F) \
+    case (F): return launch_kron64<(F), bf16>((const bf16*)x, (const bf16*)left, (const bf16*)right, (const bf16*)diag, rows, out, n_cu, stream, prep);
+    if (bf16_dtype) switch (k64_flags) {
+            FQ_K64_LIST(X)
+            default: return FQ_LAUNCH_NO_KERNEL;
+        }
+#undef X
+#define X(F) \
+    case (F): return launch_kron64<(F), f16>((const f16*)x, (const f16*)left, (const f16*)right, (const f16*)diag, rows, out, n_cu, stream, prep);
+    switch (k64_flags) {
+        FQ_K64_LIST(X) FQ_K64_RMS_LIST(X)
+        default: return FQ_LAUNCH_NO_KERNEL;
+    }
+#undef X
 }
 
 int fq_launch_kron64_prepare(const void* left, const void* right, void* image, hipStream_t stream) {

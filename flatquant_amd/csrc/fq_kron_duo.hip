@@ -31,10 +31,8 @@
 #include <type_traits>
 
 #include "fq_common.hpp"
+#include "fq_dma.hpp"   // (the group-meeting primitives: fq_lds_*, fq_meet)
 #include "fq_launch.hpp"
-#ifndef FQ_PRIO_MFMA
-#define FQ_PRIO_MFMA 2   // s_setprio level of a wave inside its GEMM phases (0: off)
-#endif
 
 namespace {
 
@@ -67,34 +65,7 @@ __device__ unsigned long long duo_trace[8 * 32 * 12];
 #define DUO_STAMP(slot)
 #endif
 
-// LDS control words through explicit ds_* instructions (a generic-pointer access would be a FLAT operation whose
-// s_waitcnt vmcnt(0) drains the loads in flight) — as in fq_kron_trio.hip.
-__device__ __forceinline__ unsigned duo_lds_read(unsigned addr) {
-    unsigned v;
-    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addr) : "memory");
-    return v;
-}
-__device__ __forceinline__ unsigned duo_lds_add_rtn(unsigned addr, unsigned val) {
-    unsigned v;
-    asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addr), "v"(val) : "memory");
-    return v;
-}
-__device__ __forceinline__ void duo_lds_write(unsigned addr, unsigned val) {
-    asm volatile("ds_write_b32 %0, %1" : : "v"(addr), "v"(val) : "memory");
-}
-// Group meeting: every wave adds one when it arrives (its own LDS traffic done) and spins until all four arrivals of this
-// meeting are in. LDS operations of one wave complete in order: a wave that sees the count sees what the others wrote before.
-__device__ __forceinline__ void duo_meet(unsigned cnt_lds, unsigned target, int lane) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (lane == 0) asm volatile("ds_add_u32 %0, %1" : : "v"(cnt_lds), "v"(1u) : "memory");
-    for (;;) {
-        unsigned v;
-        asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(cnt_lds) : "memory");
-        if ((unsigned)__builtin_amdgcn_readfirstlane((int)v) >= target) break;
-        __builtin_amdgcn_s_sleep(DUO_MEET_SLEEP);
-    }
-}
-#define DUO_MEET() { meet_n += DUO_WPG; duo_meet(meet, meet_n, lane); }
+#define DUO_MEET() { meet_n += DUO_WPG; fq_meet<DUO_MEET_SLEEP>(meet, meet_n, lane); }
 
 // FULL: M == 32 MT (128 x 224, the shape of BASELINE config 4): every DMA block is four whole instructions and no row is padding —
 // the lane-masked tail code, its scalar state (the launch spilled ~100 SGPRs to VGPR lanes) and the row tests are compiled out.
@@ -237,7 +208,7 @@ __global__ __launch_bounds__(DUO_THREADS) void fq_kron_duo_kernel(const T* __res
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     // Token claims run one token ahead: wave 0 of a group publishes the claim for token i + 1 before the group's first meeting
     // of token i; the group reads it behind the second meeting (GEMM 1 done, the buffer free) and starts the DMA at once.
-    if (wq == 0 && lane == 0) duo_lds_write(ctl_lds + 12 + grp * 4, duo_lds_add_rtn(ctl_lds + 8, 1u));
+    if (wq == 0 && lane == 0) fq_lds_write(ctl_lds + 12 + grp * 4, fq_lds_add_rtn(ctl_lds + 8, 1u));
 
     FqGroupCursor gcur;
     unsigned meet_n = 0;
@@ -315,7 +286,7 @@ __global__ __launch_bounds__(DUO_THREADS) void fq_kron_duo_kernel(const T* __res
             DUO_STAMP(2)
             DUO_MEET()   // every wave of the group has read the token: its buffer is free, the published claim is visible
             DUO_STAMP(3)
-            knext = __builtin_amdgcn_readfirstlane((int)duo_lds_read(ctl_lds + 12 + grp * 4));
+            knext = __builtin_amdgcn_readfirstlane((int)fq_lds_read(ctl_lds + 12 + grp * 4));
             more = knext < blk_cnt;
             // the next token's DMA: this wave's instructions (wq, wq + 4, ... : at most 15) go out two per K-step of GEMM 2 — a
             // VMEM issue that waits for room in the memory pipeline then waits under MFMAs already issued, not in front of them
@@ -411,7 +382,7 @@ __global__ __launch_bounds__(DUO_THREADS) void fq_kron_duo_kernel(const T* __res
             vmax = fq_uniform_f32(fmaxf(fmaxf(r0[0], r0[1]), fmaxf(r0[2], r0[3])));
             vmin = fq_uniform_f32(fminf(fminf(r1[0], r1[1]), fminf(r1[2], r1[3])));
         }
-        if (wq == 0 && lane == 0) duo_lds_write(ctl_lds + 12 + grp * 4, duo_lds_add_rtn(ctl_lds + 8, 1u));  // the claim after next (everyone has read this one)
+        if (wq == 0 && lane == 0) fq_lds_write(ctl_lds + 12 + grp * 4, fq_lds_add_rtn(ctl_lds + 8, 1u));  // the claim after next (everyone has read this one)
         // The ring is primed BEFORE this token's stores: vmcnt counts loads and stores in issue order, so a load behind the
         // stores would make the next token's first MFMA wait for their acknowledgements.
         DUO_PRIME_R()
@@ -488,11 +459,9 @@ int launch_duo(const T* x, const uint4* ws, int64_t rows, int M, const FqQuantOu
     static_assert(G::LDS <= 160 * 1024, "LDS budget");
     auto kern = fq_kron_duo_kernel<MT, FULL, T>;
     FQ_RAISE_LDS_CAP(kern, 160 * 1024);
-    int64_t blocks = (rows + DUO_GROUPS - 1) / DUO_GROUPS;
-    if (blocks > n_cu) blocks = n_cu;   // one persistent workgroup per CU
-    if (blocks < 1) blocks = 1;
-    const int64_t tpb = (rows + blocks - 1) / blocks;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(DUO_THREADS), G::LDS, stream, x, ws, rows, tpb, M, out);
+    int64_t tpb;
+    const unsigned blocks = fq_persistent_grid(rows, DUO_GROUPS, n_cu, &tpb);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(DUO_THREADS), G::LDS, stream, x, ws, rows, tpb, M, out);
     return (int)hipGetLastError();
 }
 
@@ -504,18 +473,12 @@ extern "C" int fq_duo_trace_read(void* dst) {
 }
 #endif
 
-// Returns FQ_LAUNCH_NO_KERNEL when the shape / output set is not one this kernel covers (the caller goes on to the generic kernels).
 // ws: fragment workspace already filled by fq_kron_prepare_kernel (rfrag [7][14][64], lfrag [2MT][MT][64]).
-int fq_launch_kron_duo(int flags, const f16* x, const void* ws, const f16* diag, int64_t rows, int M, int N,
-                       const FqQuantOut& out, int n_cu, hipStream_t stream) {
-    if (N != DUO_N || M <= 96 || M > 128 || diag != nullptr) return FQ_LAUNCH_NO_KERNEL;
-    if ((out.rt_flags & FQ_GROUP128) || out.post_scale != 0.0f) return FQ_LAUNCH_NO_KERNEL;
-    const bool b = (flags & FQ_DT_BF16) != 0;   // (round 4) bf16 activations and factors: the same kernel on bf16 MFMA
-    flags &= ~FQ_DT_BF16;
-    if ((flags & FQ_CT_MASK) != FQ_OUT_PACKED) return FQ_LAUNCH_NO_KERNEL;
-    const uint4* w = reinterpret_cast<const uint4*>(ws);
-    if (b) return M == 128 ? launch_duo<4, true, bf16>((const bf16*)x, w, rows, M, out, n_cu, stream)
-                           : launch_duo<4, false, bf16>((const bf16*)x, w, rows, M, out, n_cu, stream);
-    if (M == 128) return launch_duo<4, true>(x, w, rows, M, out, n_cu, stream);
-    return launch_duo<4, false>(x, w, rows, M, out, n_cu, stream);
+// fq_kron_duo_kernel<4, FULL (M = 128), T>: all four are instantiated
+int fq_launch_kron_duo(const FqKronRoute& r, const FqKronArgs& a, const FqQuantOut& out) {
+    const uint4* w = reinterpret_cast<const uint4*>(a.ws);
+    if (r.t[2]) return r.t[1] ? launch_duo<4, true, bf16>((const bf16*)a.x, w, a.rows, a.M, out, a.n_cu, a.stream)
+                              : launch_duo<4, false, bf16>((const bf16*)a.x, w, a.rows, a.M, out, a.n_cu, a.stream);
+    if (r.t[1]) return launch_duo<4, true>((const f16*)a.x, w, a.rows, a.M, out, a.n_cu, a.stream);
+    return launch_duo<4, false>((const f16*)a.x, w, a.rows, a.M, out, a.n_cu, a.stream);
 }

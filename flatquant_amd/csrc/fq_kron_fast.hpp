@@ -7,13 +7,6 @@
 #include "fq_launch.hpp"
 #include <stdlib.h>
 
-// Environment switches exist in measurement builds only (-DFQ_MEASURE, tools/microbench/*.sh): the product library reads
-// no environment variables and keeps no mutable global state.
-#ifdef FQ_MEASURE
-static inline bool fq_measure_env(const char* name) { return getenv(name) != nullptr; }
-#else
-static constexpr bool fq_measure_env(const char*) { return false; }
-#endif
 
 
 namespace {
@@ -664,10 +657,7 @@ template <int MT, int NT, int KS1, int WAVES, int OCC, bool SILU = false, int CT
           bool G128 = false>
 int launch_fast(int flags, const T* x, const uint4* ws, const T* diag, int64_t rows, int M, int N,
                 const FqQuantOut& out, int n_cu, hipStream_t stream) {
-    constexpr int PITCH = (KS1 * 2) | 1;
-    const size_t lds = (size_t)2 * MT * MT * 1024 + (size_t)MT * 32 * PITCH * 16 + (((size_t)M * N / 2 + 15) & ~(size_t)15) + 128;
-    if (lds > 160 * 1024) return FQ_LAUNCH_NO_KERNEL;
-    if (G128 != ((out.rt_flags & FQ_GROUP128) != 0)) return FQ_LAUNCH_NO_KERNEL;   // (the group epilogue is its own instantiation: registers)
+    const size_t lds = fq_kron_fast_lds(MT, KS1, M, N);   // (<= FQ_LDS_MAX, and G128 = the launch's FQ_GROUP128: fq_kron_route.hip)
     auto kern = fq_kron_fast_kernel<MT, NT, KS1, WAVES, OCC, SILU, CTF, NV, T, GM, G128>;
     FQ_RAISE_LDS_CAP(kern, 160 * 1024);
     int per_cu = (int)((160 * 1024) / lds);
@@ -681,5 +671,3 @@ int launch_fast(int flags, const T* x, const uint4* ws, const T* diag, int64_t r
 }
 
 }  // namespace
-
-static inline int tiles32(int n) { return (n + 31) / 32; }

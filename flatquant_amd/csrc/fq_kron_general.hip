@@ -417,10 +417,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void fq_kron_general_kernel(const T*
 template <int MT, int WAVES, bool LLDS, typename T>
 int launch_general_l(int flags, const T* x, const uint4* ws, const T* diag, int64_t rows, const GenGeom& g,
                    const FqQuantOut& out, int n_cu, hipStream_t stream) {
-    const size_t xs_bytes = (size_t)MT * 32 * g.pitch * 16;
-    const size_t ob = ((size_t)g.M * g.N / 2 + 15) & ~(size_t)15;
-    const size_t lds = xs_bytes + ob + 2 * WAVES * sizeof(float) + 48 + (LLDS ? (size_t)2 * MT * MT * 1024 : 0);
-    if (lds > 160 * 1024) return FQ_LAUNCH_NO_KERNEL;
+    const size_t lds = fq_kron_general_lds(MT, WAVES, LLDS, g.M, g.N);
     auto kern = fq_kron_general_kernel<MT, WAVES, LLDS, T>;
     FQ_RAISE_LDS_CAP(kern, 160 * 1024);
     int per_cu = (int)((160 * 1024) / lds);  // workgroups that fit a CU's LDS: they overlap each other's synchronous token load
@@ -434,45 +431,29 @@ int launch_general_l(int flags, const T* x, const uint4* ws, const T* diag, int6
     return (int)hipGetLastError();
 }
 
-template <int MT, int WAVES, typename T>
-int launch_general(int flags, const T* x, const uint4* ws, const T* diag, int64_t rows, const GenGeom& g,
-                   const FqQuantOut& out, int n_cu, hipStream_t stream) {
-    const int rc = launch_general_l<MT, WAVES, true, T>(flags, x, ws, diag, rows, g, out, n_cu, stream);  // L image in LDS if it fits
-    return rc != FQ_LAUNCH_NO_KERNEL ? rc : launch_general_l<MT, WAVES, false, T>(flags, x, ws, diag, rows, g, out, n_cu, stream);
-}
-
 }  // namespace
 
-// Every pair with M <= 256, even N <= 256 and M * N <= 32768. FQ_LAUNCH_NO_KERNEL outside that range.
+// Every pair with M <= 256, even N <= 256 and M * N <= 32768 whose token (and, LLDS, the L image) fits the LDS: <MT = 1 .. 8, WAVES = 4 / 8, LLDS, T>.
 // ws: fragment workspace already filled by fq_kron_prepare_kernel (fq_kron_generic.hip).
-int fq_launch_kron_general(int flags, const f16* x, const void* ws, const f16* diag, int64_t rows, int M, int N,
-                           const FqQuantOut& out, int n_cu, hipStream_t stream) {
-    if (M < 1 || N < 2 || (N & 1) || M > 256 || N > 256 || (int64_t)M * N > 32768) return FQ_LAUNCH_NO_KERNEL;
-    if (out.rt_flags & FQ_GROUP128) return FQ_LAUNCH_NO_KERNEL;
+template <int MT, typename T>
+static int launch_general(const FqKronRoute& r, const FqKronArgs& a, const GenGeom& g, const FqQuantOut& out) {
+    const uint4* w = reinterpret_cast<const uint4*>(a.ws);
+    const T *x = (const T*)a.x, *diag = (const T*)a.diag;
+    if (r.t[1] == 4) return r.t[2] ? launch_general_l<MT, 4, true, T>(a.flags, x, w, diag, a.rows, g, out, a.n_cu, a.stream)
+                                   : launch_general_l<MT, 4, false, T>(a.flags, x, w, diag, a.rows, g, out, a.n_cu, a.stream);
+    return r.t[2] ? launch_general_l<MT, 8, true, T>(a.flags, x, w, diag, a.rows, g, out, a.n_cu, a.stream)
+                  : launch_general_l<MT, 8, false, T>(a.flags, x, w, diag, a.rows, g, out, a.n_cu, a.stream);
+}
+
+int fq_launch_kron_general(const FqKronRoute& r, const FqKronArgs& a, const FqQuantOut& out) {
     GenGeom g;
-    g.M = M;
-    g.N = N;
-    g.KS1 = (N + 15) / 16;
-    g.NT = (N + 31) / 32;
+    g.M = a.M;
+    g.N = a.N;
+    g.KS1 = (a.N + 15) / 16;
+    g.NT = (a.N + 31) / 32;
     g.pitch = (g.KS1 * 2) | 1;
-    const int MT = (M + 31) / 32;
-    const uint4* w = reinterpret_cast<const uint4*>(ws);
-    if (flags & FQ_DT_BF16) {
-        flags &= ~FQ_DT_BF16;
-        const bf16* xb = (const bf16*)x;
-        const bf16* db = (const bf16*)diag;
-#define FQ_GNB(MT_)                                                                                              \
-    if (MT == MT_)                                                                                               \
-        return g.NT <= 4 ? launch_general<MT_, 4, bf16>(flags, xb, w, db, rows, g, out, n_cu, stream)            \
-                         : launch_general<MT_, 8, bf16>(flags, xb, w, db, rows, g, out, n_cu, stream);
-        FQ_GNB(1) FQ_GNB(2) FQ_GNB(3) FQ_GNB(4) FQ_GNB(5) FQ_GNB(6) FQ_GNB(7) FQ_GNB(8)
-#undef FQ_GNB
-        return FQ_LAUNCH_NO_KERNEL;
-    }
-#define FQ_GN(MT_)                                                                                        \
-    if (MT == MT_)                                                                                        \
-        return g.NT <= 4 ? launch_general<MT_, 4, f16>(flags, x, w, diag, rows, g, out, n_cu, stream)     \
-                         : launch_general<MT_, 8, f16>(flags, x, w, diag, rows, g, out, n_cu, stream);
+#define FQ_GN(MT_) \
+    if (r.t[0] == MT_) return r.t[3] ? launch_general<MT_, bf16>(r, a, g, out) : launch_general<MT_, f16>(r, a, g, out);
     FQ_GN(1) FQ_GN(2) FQ_GN(3) FQ_GN(4) FQ_GN(5) FQ_GN(6) FQ_GN(7) FQ_GN(8)
 #undef FQ_GN
     return FQ_LAUNCH_NO_KERNEL;

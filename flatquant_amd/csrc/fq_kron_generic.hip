@@ -2,9 +2,9 @@
 // pairs deployed models use whose token does not fit a wave or whose output set is not packed-only: d = 14336 (112x128),
 // 28672 (128x224), 11008 (86x128), 8192 (64x128), 7168 (64x112), 2048 (32x64), 3584 (56x64), 5120 (64x80), 18432 (128x144),
 // 27648 (144x192), 29568 (168x176), 8960 (80x112), and — packed-only, true row length as a template parameter — 18944 (128x148)
-// (function_utils.py:11-21 factor pairs); plus the fragment-image builder (fq_kron_prepare_kernel) and the launcher that
-// picks a kernel for ANY pair (fq_launch_kron_generic): wave-per-token (fq_kron_wave.hip), three token groups per CU
-// (fq_kron_trio.hip), this file's kernel, and fq_kron_general.hip for every other pair (run-time N, N % 16 != 0, M > 192).
+// (function_utils.py:11-21 factor pairs); plus the fragment-image builder (fq_kron_prepare_kernel) and fq_launch_kron, which runs
+// the kernel fq_kron_route (fq_kron_route.hip) named for a launch: the image first, then the family's launcher. WHICH kernel — the
+// order of preference among the families, their preconditions, the instantiation lists — is stated there and in fq_kron_route.hpp only.
 //
 // Same mathematics and fragment chaining as fq_kron64.hip (U = X.R rounded to fp16, Y^T = U^T.L, the C
 // fragment of GEMM 1 is the A fragment of GEMM 2), but a token no longer fits one wave's registers, so:
@@ -71,130 +71,68 @@ int fq_launch_kron_prepare(const f16* left, const f16* right, int M, int N, void
     return (int)hipGetLastError();
 }
 
-// (fq_launch_kron_generic_bf16, fq_launch_kron_g128_f16: fq_kron_generic2.hip, the bf16 and the group-128 epilogue instantiations of the same kernel)
+// The f16 instantiations without the group epilogue (bf16, group-128: fq_launch_kron_fast2, fq_kron_generic2.hip).
+template <int MT, int NT, int KS1, int W, int OCC, bool SILU>
+static int launch_fast_ct(const FqKronRoute& r, const FqKronArgs& a, const FqQuantOut& out) {
+    const f16 *x = (const f16*)a.x, *diag = (const f16*)a.diag;
+    const uint4* ws = reinterpret_cast<const uint4*>(a.ws);
+    if constexpr (SILU || MT >= 3) {   // the rows with a compile-time output set
+        if (r.t[6] == FQ_OUT_PACKED) return launch_fast<MT, NT, KS1, W, OCC, SILU, FQ_OUT_PACKED>(a.flags, x, ws, diag, a.rows, a.M, a.N, out, a.n_cu, a.stream);
+        if (r.t[6] == (FQ_OUT_PACKED | FQ_QUANT_F16))
+            return launch_fast<MT, NT, KS1, W, OCC, SILU, FQ_OUT_PACKED | FQ_QUANT_F16>(a.flags, x, ws, diag, a.rows, a.M, a.N, out, a.n_cu, a.stream);
+    }
+    return launch_fast<MT, NT, KS1, W, OCC, SILU>(a.flags, x, ws, diag, a.rows, a.M, a.N, out, a.n_cu, a.stream);
+}
+
+int fq_launch_kron_fast(const FqKronRoute& r, const FqKronArgs& a, const FqQuantOut& out) {
+    if (r.t[8] || r.t[10]) return fq_launch_kron_fast2(r, a, out);
+#define X(MT_, NT_, KS1_, W_, OCC_) \
+    if (r.t[0] == MT_ && r.t[1] == NT_ && r.t[2] == KS1_ && r.t[3] == W_) return launch_fast_ct<MT_, NT_, KS1_, W_, OCC_, true>(r, a, out);
+    if (r.t[5]) {
+        if (FQ_FS_DECODE_W != 4 && r.t[1] == 4 && r.t[3] == FQ_FS_DECODE_W)   // the decode form of 112 x 128 (fq_kron_route.hip)
+            return launch_fast<4, 4, 8, FQ_FS_DECODE_W, 1, true, FQ_OUT_PACKED>(a.flags, (const f16*)a.x, reinterpret_cast<const uint4*>(a.ws), (const f16*)a.diag,
+                                                                                a.rows, a.M, a.N, out, a.n_cu, a.stream);
+        FQ_KRON_FAST_SILU_LIST(X)
+        return FQ_LAUNCH_NO_KERNEL;
+    }
+#undef X
+#define X(MT_, NT_, KS1_, W_, OCC_, BF16_) \
+    if (r.t[0] == MT_ && r.t[1] == NT_ && r.t[2] == KS1_) return launch_fast_ct<MT_, NT_, KS1_, W_, OCC_, false>(r, a, out);
+    FQ_KRON_FAST_LIST(X)
+#undef X
+    return FQ_LAUNCH_NO_KERNEL;
+}
+
+// Which kernel: fq_kron_route. This is the rest of a launch — the fragment image, then the route's family.
+int fq_launch_kron(const FqKronRoute& r, int flags, const f16* x, const f16* left, const f16* right, const f16* diag, int64_t rows, int M, int N,
+                   const FqQuantOut& out, void* workspace, int n_cu, hipStream_t stream) {
+    if (r.rc != 0) return r.rc;
+    workspace = static_cast<unsigned char*>(workspace) + r.ws_skip;
+    if (!(flags & FQ_WS_PREPARED)) {   // the fragment image is a re-arrangement of 16-bit words: the same kernel for both types
+        const int rc = fq_launch_kron_prepare(left, right, M, N, workspace, stream);
+        if (rc != 0) return rc;
+    }
+    flags &= ~(FQ_WS_PREPARED | FQ_NO_WAVE_KERNEL | FQ_DT_BF16 | FQ_IN_SILU_MUL);
+#ifdef FQ_MEASURE
+    if (const char* dbg = getenv("FQ_KRON_DBG"))   // measurement: ablation bits of the fast kernel
+        if (r.family == FQ_KF_FAST || r.family == FQ_KF_GENERAL) flags |= atoi(dbg) & 0x7000;
+#endif
+    const FqKronArgs a = {flags, x, workspace, diag, rows, M, N, n_cu, stream};
+    switch (r.family) {
+        case FQ_KF_WAVE: return fq_launch_kron_wave(r, a, out);
+        case FQ_KF_TILES: return fq_launch_kron_tiles(r, a, out);
+        case FQ_KF_TRIO: return fq_launch_kron_trio(r, a, out);
+        case FQ_KF_DUO: return fq_launch_kron_duo(r, a, out);
+        case FQ_KF_TALL: return fq_launch_kron_tall(r, a, out);
+        case FQ_KF_FAST: return fq_launch_kron_fast(r, a, out);
+        case FQ_KF_GENERAL: return fq_launch_kron_general(r, a, out);
+    }
+    return FQ_LAUNCH_NO_KERNEL;
+}
 
 int fq_launch_kron_generic(int flags, const f16* x, const f16* left, const f16* right, const f16* diag,
                            int64_t rows, int M, int N, const FqQuantOut& out, void* workspace,
                            int64_t workspace_bytes, int n_cu, hipStream_t stream) {
-    if (M < 1 || N < 2 || (N & 1) || M > 256 || N > 256 || (int64_t)M * N > 32768) return FQ_LAUNCH_NO_KERNEL;
-    if (flags & FQ_DT_BF16)
-        return fq_launch_kron_generic_bf16(flags & ~FQ_DT_BF16, x, left, right, diag, rows, M, N, out, workspace, workspace_bytes, n_cu,
-                                           stream);
-    // the specialised kernels below: N in whole K-steps, M <= 192, 16-byte packed tokens; every other pair: fq_kron_general.hip
-    const bool spec = !(N & 15) && M <= 192 && !((M * N / 2) & 15);
-    const bool no_wave = (flags & FQ_NO_WAVE_KERNEL) != 0 || out.post_scale != 0.0f;  // (the wave kernels take no post_scale)
-    flags &= ~FQ_NO_WAVE_KERNEL;
-    if (flags & FQ_IN_SILU_MUL) {  // fused for the down_proj shapes only; said before any workspace complaint
-        if (!spec) return FQ_LAUNCH_NO_KERNEL;
-        const int mt = tiles32(M), nt = tiles32(N), ks = (N + 15) / 16;
-        if (!((mt == 4 && nt == 4 && ks == 8) || (mt == 3 && nt == 4 && ks == 8) || (mt == 4 && nt == 7 && ks == 14) ||
-              (mt == 4 && nt == 8 && ks == 16)))
-            return FQ_LAUNCH_NO_KERNEL;
-    }
-    if (!workspace || workspace_bytes < fq_kron_generic_workspace_bytes(M, N)) return FQ_LAUNCH_NEED_WS;
-    KronGeom g;
-    g.M = M;
-    g.N = N;
-    g.KS1 = (N + 15) / 16;
-    g.pitch = (g.KS1 * 2) | 1;
-    const int MT = tiles32(M), NT = tiles32(N);
-    uint4* ws = reinterpret_cast<uint4*>(workspace);
-    int rc = 0;
-    if (!(flags & FQ_WS_PREPARED)) {
-        rc = fq_launch_kron_prepare(left, right, M, N, workspace, stream);
-        if (rc != 0) return rc;
-    }
-    flags &= ~FQ_WS_PREPARED;
-    if (flags & FQ_IN_SILU_MUL) {  // x_up * silu(x_gate) formed while the token is staged: the down_proj shapes (MT >= 3)
-        flags &= ~FQ_IN_SILU_MUL;
-        if (diag != nullptr || out.in2 == nullptr) return FQ_LAUNCH_NO_KERNEL;
-#define FQ_FS(MT_, NT_, KS1_, W_, OCC_)                                                                          \
-    if (MT == MT_ && NT == NT_ && g.KS1 == KS1_) {                                                              \
-        if ((flags & FQ_CT_MASK) == FQ_OUT_PACKED && !fq_measure_env("FQ_KRON_NO_CTF"))                                 \
-            return launch_fast<MT_, NT_, KS1_, W_, OCC_, true, FQ_OUT_PACKED>(flags, x, ws, diag, rows, M, N, out, n_cu, stream); \
-        if ((flags & FQ_CT_MASK) == (FQ_OUT_PACKED | FQ_QUANT_F16) && (flags & FQ_ROUND_Y_F16))                         \
-            return launch_fast<MT_, NT_, KS1_, W_, OCC_, true, FQ_OUT_PACKED | FQ_QUANT_F16>(flags, x, ws, diag, rows, M, N, out, n_cu, stream); \
-        return launch_fast<MT_, NT_, KS1_, W_, OCC_, true>(flags, x, ws, diag, rows, M, N, out, n_cu, stream);  \
-    }
-#ifndef FQ_FS_DECODE_W
-#define FQ_FS_DECODE_W 8   // (measurement knob) waves of the decode-sized 112 x 128 SiLU.mul launch; 4 = the prefill build at every size
-#endif
-        // decode-sized (a handful of tokens, one workgroup each, the chip idle around them): eight waves per token — the four without an
-        // n'-tile halve the rounds of the image copy and of the token's loads (a latency chain, not bandwidth)
-        if (FQ_FS_DECODE_W != 4 && rows <= 64 && MT == 4 && NT == 4 && g.KS1 == 8 && (flags & FQ_CT_MASK) == FQ_OUT_PACKED)
-            return launch_fast<4, 4, 8, FQ_FS_DECODE_W, 1, true, FQ_OUT_PACKED>(flags, x, ws, diag, rows, M, N, out, n_cu, stream);
-        FQ_FS(4, 4, 8, 4, 2) FQ_FS(3, 4, 8, 4, 2) FQ_FS(4, 7, 14, 8, 1) FQ_FS(4, 8, 16, 8, 1)
-#undef FQ_FS
-        return FQ_LAUNCH_NO_KERNEL;
-    }
-    if (flags & FQ_IN_RMSNORM) {   // fused RMSNorm: the wave-per-token kernel (packed output) is the one that has it
-        if (!spec || no_wave || diag != nullptr) return FQ_LAUNCH_NO_KERNEL;
-        return fq_launch_kron_wave(flags, x, ws, diag, rows, M, N, out, n_cu, stream);
-    }
-    if (spec && !no_wave && !fq_measure_env("FQ_KRON_NO_WAVE")) {  // one wave per token where a token fits a wave (packed output only)
-        rc = fq_launch_kron_wave(flags, x, ws, diag, rows, M, N, out, n_cu, stream);
-        if (rc != FQ_LAUNCH_NO_KERNEL) return rc;
-    }
-    // per-128-element scales: the wave kernel above (N = 64, packed, fp32 accumulator) or the group epilogue of the
-    // workgroup-per-token kernel's all-output-sets instantiations (the transform rounded to the activation dtype)
-    const bool g128 = (out.rt_flags & FQ_GROUP128) != 0;
-    if (g128 && (!(flags & FQ_ROUND_Y_F16) || !spec)) return FQ_LAUNCH_NO_KERNEL;
-    if (!g128 && spec && !fq_measure_env("FQ_KRON_NO_TILES")) { // 80 x 112, 86 x 128, 128 x 144, 144 x 192 (round 4): token groups of NT waves
-        rc = fq_launch_kron_tiles(flags, x, ws, diag, rows, M, N, out, n_cu, stream);
-        if (rc != FQ_LAUNCH_NO_KERNEL) return rc;
-    }
-    if (!g128 && spec && !fq_measure_env("FQ_KRON_NO_TRIO")) {  // 64 < M <= 128, N = 128, packed output: three token groups one phase apart
-        rc = fq_launch_kron_trio(flags, x, ws, diag, rows, M, N, out, n_cu, stream);
-        if (rc != FQ_LAUNCH_NO_KERNEL) return rc;
-    }
-    if (!g128 && spec && !fq_measure_env("FQ_KRON_NO_DUO")) {   // 96 < M <= 128, N = 224, packed output: two token groups per CU
-        rc = fq_launch_kron_duo(flags, x, ws, diag, rows, M, N, out, n_cu, stream);
-        if (rc != FQ_LAUNCH_NO_KERNEL) return rc;
-    }
-    if (!g128 && spec && !fq_measure_env("FQ_KRON_NO_TALL")) {  // 64 < M <= 192, N = 64, packed output: a wave per ROW tile (172 x 64: Hadamard 11008)
-        rc = fq_launch_kron_tall(flags, x, ws, diag, rows, M, N, out, n_cu, stream);
-        if (rc != FQ_LAUNCH_NO_KERNEL) return rc;
-    }
-#ifdef FQ_MEASURE
-    if (const char* dbg = getenv("FQ_KRON_DBG")) flags |= atoi(dbg) & 0x7000;  // measurement: ablation bits of the fast kernel
-#endif
-    if (!g128 && N == 148 && !fq_measure_env("FQ_KRON_NO_TILES")) {   // (round 4) 128 x 148 on token groups of five waves
-        rc = fq_launch_kron_tiles(flags, x, ws, diag, rows, M, N, out, n_cu, stream);
-        if (rc != FQ_LAUNCH_NO_KERNEL) return rc;
-    }
-    // N % 16 != 0 in the workgroup-per-token kernel: the packed-only launch of 96 < M <= 128, N = 148 (18944 = 128 x 148,
-    // Qwen2.5-7B ffn); its other output sets, diag and every other such pair: fq_kron_general.hip
-    if (!g128 && N == 148 && MT == 4 && (flags & FQ_CT_MASK) == FQ_OUT_PACKED && diag == nullptr && !((M * N / 2) & 15) &&
-        !fq_measure_env("FQ_KRON_NO_CTF"))
-        return launch_fast<4, 5, 10, 8, 1, false, FQ_OUT_PACKED, 148>(flags, x, ws, diag, rows, M, N, out, n_cu, stream);
-    if (g128) return fq_launch_kron_g128_f16(flags, x, ws, diag, rows, M, N, out, n_cu, stream);   // (fq_kron_generic2.hip)
-    if (spec) {
-#define FQ_F(MT_, NT_, KS1_, W_, OCC_)                                                                   \
-    if (MT == MT_ && NT == NT_ && g.KS1 == KS1_) {                                                       \
-        if (!g128 && MT_ >= 3 && (flags & FQ_CT_MASK) == FQ_OUT_PACKED && !fq_measure_env("FQ_KRON_NO_CTF"))    \
-            rc = launch_fast<MT_, NT_, KS1_, W_, OCC_, false, (MT_ >= 3 ? FQ_OUT_PACKED : -1)>(flags, x, ws, diag, rows, M, N, out, n_cu, stream); \
-        else if (!g128 && MT_ >= 3 && (flags & FQ_CT_MASK) == (FQ_OUT_PACKED | FQ_QUANT_F16) && (flags & FQ_ROUND_Y_F16)) \
-            rc = launch_fast<MT_, NT_, KS1_, W_, OCC_, false, (MT_ >= 3 ? (FQ_OUT_PACKED | FQ_QUANT_F16) : -1)>(flags, x, ws, diag, rows, M, N, out, n_cu, stream); \
-        else                                                                                             \
-            rc = launch_fast<MT_, NT_, KS1_, W_, OCC_>(flags, x, ws, diag, rows, M, N, out, n_cu, stream); \
-        if (rc != FQ_LAUNCH_NO_KERNEL) return rc;                                                                      \
-    }
-#ifndef FQ_GEN_OCC2
-#define FQ_GEN_OCC2 2   // MT = 2 shapes (measurement knobs): workgroups per CU, waves per workgroup
-#endif
-#ifndef FQ_GEN_W2
-#define FQ_GEN_W2 4
-#endif
-        FQ_F(2, 4, 8, FQ_GEN_W2, FQ_GEN_OCC2) FQ_F(4, 4, 8, 4, 2) FQ_F(3, 4, 8, 4, 2) FQ_F(4, 7, 14, 8, 1) FQ_F(2, 4, 7, FQ_GEN_W2, FQ_GEN_OCC2)
-        FQ_F(4, 8, 16, 8, 1)  // 112 x 256: the Hadamard rotation of 28672 = (28 x 4) x 256 as a Kronecker product
-        FQ_F(1, 2, 4, 4, 4) FQ_F(2, 2, 4, 4, FQ_GEN_OCC2) FQ_F(2, 3, 5, 4, FQ_GEN_OCC2)
-        FQ_F(4, 5, 9, 8, 1)   // 128 x 144 = 18432 (DeepSeek-V3 dense ffn), and every 96 < M <= 128 with N = 144
-        FQ_F(3, 4, 7, 4, 2)   // 80 x 112 = 8960 (Qwen2.5-1.5B ffn)
-        FQ_F(1, 2, 3, 4, 4)   // 32 x 48 = 1536 (Qwen2.5-1.5B hidden)
-        FQ_F(5, 6, 12, 8, 1)  // 144 x 192 = 27648 (Qwen2.5-32B ffn)
-        FQ_F(6, 6, 11, 8, 1)  // 168 x 176 = 29568 (Qwen2.5-72B ffn)
-#undef FQ_F
-    }
-    if (g128) return FQ_LAUNCH_NO_KERNEL;   // (the general kernel has no group epilogue)
-    return fq_launch_kron_general(flags, x, ws, diag, rows, M, N, out, n_cu, stream);
+    const FqKronRoute r = fq_kron_route(flags, rows, M, N, diag != nullptr, out, workspace ? workspace_bytes : 0, false, fq_kron_measure_mask());
+    return fq_launch_kron(r, flags, x, left, right, diag, rows, M, N, out, workspace, n_cu, stream);
 }

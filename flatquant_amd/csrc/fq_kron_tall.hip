@@ -330,31 +330,12 @@ int launch_tall(const f16* x, const uint4* ws, int64_t rows, int M, const FqQuan
 
 }  // namespace
 
-// Returns FQ_LAUNCH_NO_KERNEL when the shape / output set is not one this kernel covers (the caller goes on to the generic kernels).
 // ws: fragment workspace already filled by fq_kron_prepare_kernel (rfrag [2][4][64], lfrag [2MT][MT][64]).
-int fq_launch_kron_tall(int flags, const f16* x, const void* ws, const f16* diag, int64_t rows, int M, int N,
-                        const FqQuantOut& out, int n_cu, hipStream_t stream) {
-    if (N != TALL_N || M <= 64 || M > 192 || diag != nullptr) return FQ_LAUNCH_NO_KERNEL;
-    if ((out.rt_flags & FQ_GROUP128) || out.ws_group_stride != 0) return FQ_LAUNCH_NO_KERNEL;
-    const int ct = flags & FQ_CT_MASK, cq = ct & ~FQ_OUT_TRANSFORM;
-    const bool yout = (ct & FQ_OUT_TRANSFORM) != 0;
-    // (round 4) the transform ALONE (kronecker_matmul; the rotation of matmul_hadU_cuda run as a Kronecker pair): the fp16-epilogue
-    // instantiation with no clip set — the quantiser loop does not run, the rounded pairs go out as they are
-    const bool yonly = yout && (cq & ~FQ_QUANT_F16) == 0 && out.n_clips == 0;
-    const bool h16 = yonly || (cq == (FQ_OUT_PACKED | FQ_QUANT_F16) && (flags & FQ_ROUND_Y_F16));
-    if (cq != FQ_OUT_PACKED && !h16) return FQ_LAUNCH_NO_KERNEL;
-    if (yout && out.y == nullptr) return FQ_LAUNCH_NO_KERNEL;
-    const uint4* wp = reinterpret_cast<const uint4*>(ws);
-    const int MT = (M + 31) / 32;
-#define FQ_TALL(MT_)                                                                                              \
-    if (MT == MT_) {                                                                                              \
-        if (yout)                                                                                                 \
-            return h16 ? launch_tall<MT_, true, true>(x, wp, rows, M, out, n_cu, stream)                          \
-                       : launch_tall<MT_, false, true>(x, wp, rows, M, out, n_cu, stream);                        \
-        return h16 ? launch_tall<MT_, true, false>(x, wp, rows, M, out, n_cu, stream)                             \
-                   : launch_tall<MT_, false, false>(x, wp, rows, M, out, n_cu, stream);                           \
-    }
-    FQ_TALL(3) FQ_TALL(4) FQ_TALL(5) FQ_TALL(6)
-#undef FQ_TALL
+int fq_launch_kron_tall(const FqKronRoute& r, const FqKronArgs& a, const FqQuantOut& out) {
+#define X(MT_, H16_, YOUT_)                                           \
+    if (r.t[0] == MT_ && r.t[1] == H16_ && r.t[2] == YOUT_)           \
+        return launch_tall<MT_, H16_, YOUT_>((const f16*)a.x, reinterpret_cast<const uint4*>(a.ws), a.rows, a.M, out, a.n_cu, a.stream);
+    FQ_KRON_TALL_LIST(X)
+#undef X
     return FQ_LAUNCH_NO_KERNEL;
 }

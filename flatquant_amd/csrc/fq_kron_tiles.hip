@@ -25,29 +25,17 @@
 // bit-identical to the workgroup-per-token kernel (tests/test_gpu_kron_tiles.py). Measurements: profiles/r04_tiles_timing.txt,
 // r04_kron_128x144_pmc.txt.
 #include "fq_common.hpp"
-#ifndef FQ_PRIO_MFMA
-#define FQ_PRIO_MFMA 2   // s_setprio level of a wave inside its GEMM phases (0: off); see fq_kron_duo.hip
-#endif
 #include "fq_dma.hpp"
 #include "fq_launch.hpp"
 
 namespace {
 
-// measurement knobs (tools/variants.sh): groups of the 80 x 112 launch, A fragments in flight, streamed R at N = 144
-#ifndef TILES_G112
-#define TILES_G112 4   // (measured: 3 groups 113 us, 4 groups 107.5 us per 16384 tokens of 80 x 112; 121-127 VGPRs with four A fragments in flight)
-#endif
+// measurement knobs (tools/variants.sh): A fragments in flight (the group counts and streamed R at N = 144: fq_kron_route.hpp)
 #ifndef TILES_DA
 #define TILES_DA 0   // 0: the per-geometry default below
 #endif
 #ifndef TILES_DB
 #define TILES_DB 0   // 0: the default below (2)
-#endif
-#ifndef TILES_G144
-#define TILES_G144 2
-#endif
-#ifndef TILES_RS144
-#define TILES_RS144 false
 #endif
 #ifndef TILES_ABL
 #define TILES_ABL 0   // measurement builds: 1 no quantiser, 2 no GEMM 1, 4 no GEMM 2, 8 no stores, 16 no DMA after the first
@@ -88,31 +76,7 @@ struct TilesGeom {
     static_assert(N % 4 == 0 && (LKS * 16 * N * 2) % 16 == 0 && NT == (N + 31) / 32 && LKS <= 2 * MT && LKS > 2 * MT - 2 && GROUPS <= 4 && NT <= 8, "geometry");
 };
 
-__device__ __forceinline__ unsigned tl_lds_read(unsigned addr) {
-    unsigned v;
-    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addr) : "memory");
-    return v;
-}
-__device__ __forceinline__ unsigned tl_lds_add_rtn(unsigned addr, unsigned val) {
-    unsigned v;
-    asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addr), "v"(val) : "memory");
-    return v;
-}
-__device__ __forceinline__ void tl_lds_write(unsigned addr, unsigned val) {
-    asm volatile("ds_write_b32 %0, %1" : : "v"(addr), "v"(val) : "memory");
-}
-// group meeting on a counter in LDS (fq_kron_trio.hip: trio_meet)
-__device__ __forceinline__ void tl_meet(unsigned cnt_lds, unsigned target, int lane) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (lane == 0) asm volatile("ds_add_u32 %0, %1" : : "v"(cnt_lds), "v"(1u) : "memory");
-    for (;;) {
-        unsigned v;
-        asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(cnt_lds) : "memory");
-        if ((unsigned)__builtin_amdgcn_readfirstlane((int)v) >= target) break;
-        __builtin_amdgcn_s_sleep(1);
-    }
-}
-#define TILES_MEET() { meet_n += NT; tl_meet(meet, meet_n, lane); }
+#define TILES_MEET() { meet_n += NT; fq_meet(meet, meet_n, lane); }
 
 // per-lane source offset of DMA instruction i (which fills the LDS slots [64 i, 64 i + 64) linearly), relative to the
 // instruction's own KB and biased by +128 bytes (an XOR moves a lane at most 7 chunks back: never negative)
@@ -281,9 +245,9 @@ __global__ __launch_bounds__(GROUPS * NT * 64) void fq_kron_tiles_kernel(const T
         }
 
         // ================= phase B: next token's DMA, GEMM 2 (Y^T = U^T . L), extrema =================
-        if (wq == 0 && lane == 0) tl_lds_write(ctl_lds + 20 + grp * 4, tl_lds_add_rtn(ctl_lds + 16, 1u));   // claim the group's next token
+        if (wq == 0 && lane == 0) fq_lds_write(ctl_lds + 20 + grp * 4, fq_lds_add_rtn(ctl_lds + 16, 1u));   // claim the group's next token
         TILES_MEET()   // A|B: the group has read its token buffer
-        const int knext = __builtin_amdgcn_readfirstlane((int)tl_lds_read(ctl_lds + 20 + grp * 4));
+        const int knext = __builtin_amdgcn_readfirstlane((int)fq_lds_read(ctl_lds + 20 + grp * 4));
         const bool more = !(TILES_ABL & 16) && knext < blk_cnt && dn > 0;
         if (more) stage_token(knext);
         if (knext < blk_cnt) prime_r();   // (behind the DMA in the queue; first used after phase C's vmcnt(0))
@@ -497,96 +461,35 @@ template <int MT, int NT, int N, int GROUPS, int LKS, bool RS, typename T, bool 
 int launch_tiles_t(const T* x, const uint4* ws, int64_t rows, int M, const FqQuantOut& out, int n_cu, hipStream_t stream) {
     typedef TilesGeom<MT, NT, N, GROUPS, LKS> G;
     static_assert(G::LDS <= 160 * 1024, "LDS budget");
-    int64_t blocks = (rows + GROUPS - 1) / GROUPS;
-    if (blocks > n_cu) blocks = n_cu;   // one persistent workgroup per CU
-    if (blocks < 1) blocks = 1;
-    const int64_t tpb = (rows + blocks - 1) / blocks;
-    hipLaunchKernelGGL((fq_kron_tiles_kernel<MT, NT, N, GROUPS, LKS, RS, T, H16>), dim3((unsigned)blocks), dim3(G::THREADS), 0, stream, x, ws,
+    int64_t tpb;
+    const unsigned blocks = fq_persistent_grid(rows, GROUPS, n_cu, &tpb);
+    hipLaunchKernelGGL((fq_kron_tiles_kernel<MT, NT, N, GROUPS, LKS, RS, T, H16>), dim3(blocks), dim3(G::THREADS), 0, stream, x, ws,
                        rows, tpb, M, out);
     return (int)hipGetLastError();
 }
-template <int MT, int NT, int N, int GROUPS, int LKS, bool RS>
-int launch_tiles(bool is_bf16, const f16* x, const uint4* ws, int64_t rows, int M, const FqQuantOut& out, int n_cu, hipStream_t stream) {
-    return is_bf16 ? launch_tiles_t<MT, NT, N, GROUPS, LKS, RS, bf16>((const bf16*)x, ws, rows, M, out, n_cu, stream)
-                   : launch_tiles_t<MT, NT, N, GROUPS, LKS, RS, f16>(x, ws, rows, M, out, n_cu, stream);
-}
-
 }  // namespace
 
-// Returns FQ_LAUNCH_NO_KERNEL when the shape / output set is not one this kernel covers (the caller goes on to the workgroup-per-token kernel).
 // ws: fragment workspace already filled by fq_kron_prepare_kernel (rfrag [NT][KS1][64], lfrag [2MT][MT][64]).
-// flags & FQ_DT_BF16: bf16 activations and factors (the same geometry; bf16 MFMA and rounding points). On bf16 this kernel also takes
-// N = 128 (112 x 128, 86 x 128: fq_kron_trio.hip is fp16-only) — three groups of four waves, as there.
-int fq_launch_kron_tiles(int flags, const f16* x, const void* ws, const f16* diag, int64_t rows, int M, int N,
-                         const FqQuantOut& out, int n_cu, hipStream_t stream) {
-    const bool b = (flags & FQ_DT_BF16) != 0;
-    flags &= ~FQ_DT_BF16;
-    if (diag != nullptr || (out.rt_flags & FQ_GROUP128)) return FQ_LAUNCH_NO_KERNEL;
-    const uint4* w = reinterpret_cast<const uint4*>(ws);
-    const int lks = (M + 15) >> 4;
-#ifndef TILES_N64
-#define TILES_N64 1   // 0: the tall pairs stay with fq_kron_tall.hip (A/B builds)
-#endif
-    if (TILES_N64 && N == 64 && M > 64 && M <= 192 && !b && out.ws_group_stride == 0) {
-        // (round 5) the TALL pairs — Hadamard rotations as a Kronecker launch — on two-wave token groups. Output sets: packed with the fp32
-        // quantiser, or the fp16 Quantizer arithmetic (H16: packed and / or the rounded transform, the launches of ops.hadamard_quant /
-        // hadamard_quantizer / hadamard at 11008, 8960, 5120 ...); the fp32 quantiser WITH the transform (a test-only set) stays with fq_kron_tall.hip
-        const int ct = flags & FQ_CT_MASK, cq = ct & ~FQ_OUT_TRANSFORM;
-        const bool yout = (ct & FQ_OUT_TRANSFORM) != 0;
-        const bool yonly = yout && (cq & ~FQ_QUANT_F16) == 0 && out.n_clips == 0;
-        const bool h16 = yonly || (cq == (FQ_OUT_PACKED | FQ_QUANT_F16) && (flags & FQ_ROUND_Y_F16));
-        if (yout && (out.y == nullptr || !h16)) return FQ_LAUNCH_NO_KERNEL;
-        if (!h16 && cq != FQ_OUT_PACKED) return FQ_LAUNCH_NO_KERNEL;
-        // (measured, profiles/r05_tall_on_tiles.txt) the rotation ALONE (no clip set: 4 d bytes per token, 32-byte pieces of 128-byte rows from every
-        // lane) is slower here than on the row-split kernel at six row tiles — 172 x 64: 180 against 171 us — and level or faster below
-        if (yonly && M > 160) return FQ_LAUNCH_NO_KERNEL;
+int fq_launch_kron_tiles(const FqKronRoute& r, const FqKronArgs& a, const FqQuantOut& out) {
+    const f16* x = (const f16*)a.x;
+    const uint4* w = reinterpret_cast<const uint4*>(a.ws);
+    if (r.t[2] == 64) {
         FqQuantOut o2 = out;
-        if (!yout) o2.y = nullptr;   // (the kernel writes the transform whenever out.y is given)
-        const int MT = (M + 31) / 32;
-#define FQ_T64(MT_, LKS_, G_)                                                                                               \
-    if (MT == MT_ && lks == LKS_)                                                                                          \
-        return h16 ? launch_tiles_t<MT_, 2, 64, G_, LKS_, false, f16, true>(x, w, rows, M, o2, n_cu, stream)               \
-                   : launch_tiles_t<MT_, 2, 64, G_, LKS_, false, f16, false>(x, w, rows, M, o2, n_cu, stream);
-        // four groups of two waves where 4 tokens + the L image fit 160 KB (a token: 2 LKS KB, the image: LKS x MT KB); 172 x 64 = 88 + 66 KB
-#ifndef TILES_G64
-#define TILES_G64 4   // (measurement knob) token groups of the 172 x 64 launch
-#endif
-        FQ_T64(3, 5, 4) FQ_T64(3, 6, 4) FQ_T64(4, 7, 4) FQ_T64(4, 8, 4) FQ_T64(5, 9, 4) FQ_T64(5, 10, 4) FQ_T64(6, 11, TILES_G64) FQ_T64(6, 12, 3)
-#undef FQ_T64
+        if (!(a.flags & FQ_OUT_TRANSFORM)) o2.y = nullptr;   // (the kernel writes the transform whenever out.y is given)
+#define X(MT_, LKS_, G_)                                                                                                    \
+    if (r.t[0] == MT_ && r.t[4] == LKS_)                                                                                   \
+        return r.t[7] ? launch_tiles_t<MT_, 2, 64, G_, LKS_, false, f16, true>(x, w, a.rows, a.M, o2, a.n_cu, a.stream)    \
+                      : launch_tiles_t<MT_, 2, 64, G_, LKS_, false, f16, false>(x, w, a.rows, a.M, o2, a.n_cu, a.stream);
+        FQ_KRON_TILES64_LIST(X)
+#undef X
         return FQ_LAUNCH_NO_KERNEL;
     }
-    if ((flags & FQ_CT_MASK) != FQ_OUT_PACKED) return FQ_LAUNCH_NO_KERNEL;
-    if (N == 112 && M > 64 && M <= 96) {   // 80 x 112: four groups of four waves
-        return lks == 5 ? launch_tiles<3, 4, 112, TILES_G112, 5, false>(b, x, w, rows, M, out, n_cu, stream)
-                        : launch_tiles<3, 4, 112, TILES_G112, 6, false>(b, x, w, rows, M, out, n_cu, stream);
+#define X(MT_, NT_, N_, G_, LKS_, RS_, F16_)                                                                                \
+    if (r.t[2] == N_ && r.t[0] == MT_ && r.t[4] == LKS_) {                                                                 \
+        if (r.t[6]) return launch_tiles_t<MT_, NT_, N_, G_, LKS_, RS_, bf16>((const bf16*)x, w, a.rows, a.M, out, a.n_cu, a.stream); \
+        if constexpr (F16_) return launch_tiles_t<MT_, NT_, N_, G_, LKS_, RS_, f16>(x, w, a.rows, a.M, out, a.n_cu, a.stream);       \
     }
-    if (N == 144 && M > 96 && M <= 128) {  // 128 x 144: two groups of five waves
-        return lks == 7 ? launch_tiles<4, 5, 144, TILES_G144, 7, TILES_RS144>(b, x, w, rows, M, out, n_cu, stream)
-                        : launch_tiles<4, 5, 144, TILES_G144, 8, TILES_RS144>(b, x, w, rows, M, out, n_cu, stream);
-    }
-    if (N == 192 && M > 128 && M <= 144) { // 144 x 192: two groups of six waves, R streamed; 160 KB hold nine K-steps of L
-        return launch_tiles<5, 6, 192, 2, 9, true>(b, x, w, rows, M, out, n_cu, stream);
-    }
-    if (N == 148 && M > 96 && M <= 128 && !(M & 1)) {   // 128 x 148 (18944, Qwen2.5-7B ffn): two groups of five waves, rows of 296 bytes
-        return lks == 7 ? launch_tiles<4, 5, 148, 2, 7, false>(b, x, w, rows, M, out, n_cu, stream)
-                        : launch_tiles<4, 5, 148, 2, 8, false>(b, x, w, rows, M, out, n_cu, stream);
-    }
-    if (N == 176 && M > 160 && M <= 192) { // 168 x 176 (29568, Qwen2.5-72B ffn): ONE group of six waves (two tokens + the L image would need 184 KB);
-                                           // the next token's DMA still runs under GEMM 2 and the quantiser
-        return lks == 11 ? launch_tiles<6, 6, 176, 1, 11, false>(b, x, w, rows, M, out, n_cu, stream)
-                         : launch_tiles<6, 6, 176, 1, 12, false>(b, x, w, rows, M, out, n_cu, stream);
-    }
-    if (N == 128 && M > 64 && M <= 96) {    // 86 x 128 (11008, Llama-2-7B ffn), fp16 and bf16: 123 us where fq_kron_trio.hip's MT = 3 build takes 145
-        return lks == 5 ? launch_tiles<3, 4, 128, 3, 5, false>(b, x, w, rows, M, out, n_cu, stream)
-                        : launch_tiles<3, 4, 128, 3, 6, false>(b, x, w, rows, M, out, n_cu, stream);
-    }
-#ifdef TILES_G128X4   // measurement: 112 x 128 on FOUR groups of four waves (R streamed; 28 KB per token without zero rows + 28 KB of L = 140 KB)
-    if (N == 128 && M > 96 && M <= 112)
-        return launch_tiles<4, 4, 128, 4, 7, true>(b, x, w, rows, M, out, n_cu, stream);
-#endif
-    if (b && N == 128 && M > 96 && M <= 128) {   // bf16 112 x 128: three groups of four waves (fp16: fq_kron_trio.hip, the same speed)
-        return lks == 7 ? launch_tiles_t<4, 4, 128, 3, 7, false, bf16>((const bf16*)x, w, rows, M, out, n_cu, stream)
-                        : launch_tiles_t<4, 4, 128, 3, 8, false, bf16>((const bf16*)x, w, rows, M, out, n_cu, stream);
-    }
+    FQ_KRON_TILES_LIST(X)
+#undef X
     return FQ_LAUNCH_NO_KERNEL;
 }

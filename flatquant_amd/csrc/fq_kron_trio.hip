@@ -25,9 +25,6 @@
 // (fq_kron_prepare_kernel). Everything this kernel does not take (fp16 outputs, SiLU.mul input, diag, per-128 scales)
 // stays with fq_kron_generic.hip. What limits it is in DESIGN.md 4.2 (the shader clock under this load).
 #include "fq_common.hpp"
-#ifndef FQ_PRIO_MFMA
-#define FQ_PRIO_MFMA 2   // s_setprio level of a wave inside its GEMM phases (0: off)
-#endif
 #include "fq_dma.hpp"
 #include "fq_launch.hpp"
 
@@ -64,36 +61,7 @@ __device__ unsigned long long trio_trace[12 * 32 * 12];
 #define TRIO_STAMP(slot)
 #endif
 
-// LDS control words are touched through explicit ds_* instructions: a generic-pointer access would be a FLAT operation,
-// whose s_waitcnt vmcnt(0) drains the DMA in flight.
-__device__ __forceinline__ unsigned trio_lds_read(unsigned addr) {
-    unsigned v;
-    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addr) : "memory");
-    return v;
-}
-__device__ __forceinline__ unsigned trio_lds_add_rtn(unsigned addr, unsigned val) {
-    unsigned v;
-    asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addr), "v"(val) : "memory");
-    return v;
-}
-__device__ __forceinline__ void trio_lds_write(unsigned addr, unsigned val) {
-    asm volatile("ds_write_b32 %0, %1" : : "v"(addr), "v"(val) : "memory");
-}
-
-// Group meeting on a counter in LDS: every wave adds one when it arrives (its own LDS traffic done) and spins until the
-// four arrivals of this meeting are in. LDS operations of one wave complete in order, so a wave that sees the count
-// also sees what the others wrote before arriving.
-__device__ __forceinline__ void trio_meet(unsigned cnt_lds, unsigned target, int lane) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (lane == 0) asm volatile("ds_add_u32 %0, %1" : : "v"(cnt_lds), "v"(1u) : "memory");
-    for (;;) {
-        unsigned v;
-        asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(cnt_lds) : "memory");
-        if ((unsigned)__builtin_amdgcn_readfirstlane((int)v) >= target) break;
-        __builtin_amdgcn_s_sleep(1);
-    }
-}
-#define TRIO_MEET() { meet_n += 4; trio_meet(meet, meet_n, lane); }
+#define TRIO_MEET() { meet_n += 4; fq_meet(meet, meet_n, lane); }
 
 template <int MT, bool H16, bool TAIL>
 __global__ __launch_bounds__(TRIO_THREADS) void fq_kron_trio_kernel(const f16* __restrict__ x, const uint4* __restrict__ ws,
@@ -205,11 +173,11 @@ __global__ __launch_bounds__(TRIO_THREADS) void fq_kron_trio_kernel(const f16* _
         }
 
         // ================= phase B: next token's DMA, GEMM 2 (Y^T = U^T . L), extrema =================
-        if (wq == 0 && lane == 0) trio_lds_write(ctl_lds + 16 + grp * 4, trio_lds_add_rtn(ctl_lds + 12, 1u));  // claim the group's next token; published by the meeting
+        if (wq == 0 && lane == 0) fq_lds_write(ctl_lds + 16 + grp * 4, fq_lds_add_rtn(ctl_lds + 12, 1u));  // claim the group's next token; published by the meeting
         TRIO_STAMP(2)
         TRIO_MEET()  // A|B: the group has read its token buffer
         TRIO_STAMP(3)
-        const int knext = __builtin_amdgcn_readfirstlane((int)trio_lds_read(ctl_lds + 16 + grp * 4));
+        const int knext = __builtin_amdgcn_readfirstlane((int)fq_lds_read(ctl_lds + 16 + grp * 4));
         const bool more = !(TRIO_ABL & 16) && knext < blk_cnt && dn > 0;
         {
             // per-lane DMA offsets (dma_span_offsets for CPR = 16, in closed form): slot q = 64 i + lane -> row 4 i + lane / 16,
@@ -393,22 +361,14 @@ __global__ __launch_bounds__(TRIO_THREADS) void fq_kron_trio_kernel(const f16* _
 }
 
 template <int MT, bool H16, bool TAIL>
-int launch_trio_t(const f16* x, const uint4* ws, int64_t rows, int M, const FqQuantOut& out, int n_cu, hipStream_t stream) {
+int launch_trio(const f16* x, const uint4* ws, int64_t rows, int M, const FqQuantOut& out, int n_cu, hipStream_t stream) {
     typedef TrioGeom<MT> G;
     static_assert(G::LDS <= 160 * 1024, "LDS budget");
-    int64_t blocks = (rows + TRIO_GROUPS - 1) / TRIO_GROUPS;
-    if (blocks > n_cu) blocks = n_cu;  // one persistent workgroup per CU
-    if (blocks < 1) blocks = 1;
-    const int64_t tpb = (rows + blocks - 1) / blocks;
-    hipLaunchKernelGGL((fq_kron_trio_kernel<MT, H16, TAIL>), dim3((unsigned)blocks), dim3(TRIO_THREADS), 0, stream, x, ws, rows, tpb,
+    int64_t tpb;
+    const unsigned blocks = fq_persistent_grid(rows, TRIO_GROUPS, n_cu, &tpb);
+    hipLaunchKernelGGL((fq_kron_trio_kernel<MT, H16, TAIL>), dim3(blocks), dim3(TRIO_THREADS), 0, stream, x, ws, rows, tpb,
                        M, out);
     return (int)hipGetLastError();
-}
-
-template <int MT, bool H16>
-int launch_trio(const f16* x, const uint4* ws, int64_t rows, int M, const FqQuantOut& out, int n_cu, hipStream_t stream) {
-    return (M & 3) ? launch_trio_t<MT, H16, true>(x, ws, rows, M, out, n_cu, stream)
-                   : launch_trio_t<MT, H16, false>(x, ws, rows, M, out, n_cu, stream);
 }
 
 }  // namespace
@@ -419,16 +379,15 @@ extern "C" int fq_trio_trace_read(void* dst) {
 }
 #endif
 
-// Returns FQ_LAUNCH_NO_KERNEL when the shape / output set is not one this kernel covers (the caller goes on to the generic kernels).
 // ws: fragment workspace already filled by fq_kron_prepare_kernel (rfrag [4][8][64], lfrag [2MT][MT][64]).
-int fq_launch_kron_trio(int flags, const f16* x, const void* ws, const f16* diag, int64_t rows, int M, int N,
-                        const FqQuantOut& out, int n_cu, hipStream_t stream) {
-    if (N != 128 || M <= 64 || M > 128 || diag != nullptr) return FQ_LAUNCH_NO_KERNEL;
-    if (out.rt_flags & FQ_GROUP128) return FQ_LAUNCH_NO_KERNEL;
-    const int ct = flags & FQ_CT_MASK;
-    const bool h16 = ct == (FQ_OUT_PACKED | FQ_QUANT_F16) && (flags & FQ_ROUND_Y_F16);
-    if (ct != FQ_OUT_PACKED && !h16) return FQ_LAUNCH_NO_KERNEL;
-    const uint4* w = reinterpret_cast<const uint4*>(ws);
-    if (M > 96) return h16 ? launch_trio<4, true>(x, w, rows, M, out, n_cu, stream) : launch_trio<4, false>(x, w, rows, M, out, n_cu, stream);
-    return h16 ? launch_trio<3, true>(x, w, rows, M, out, n_cu, stream) : launch_trio<3, false>(x, w, rows, M, out, n_cu, stream);
+int fq_launch_kron_trio(const FqKronRoute& r, const FqKronArgs& a, const FqQuantOut& out) {
+    const f16* x = (const f16*)a.x;
+    const uint4* w = reinterpret_cast<const uint4*>(a.ws);
+#define X(MT_, H16_)                                                                                     \
+    if (r.t[0] == MT_ && r.t[1] == H16_)                                                                \
+        return r.t[2] ? launch_trio<MT_, H16_, true>(x, w, a.rows, a.M, out, a.n_cu, a.stream)           \
+                      : launch_trio<MT_, H16_, false>(x, w, a.rows, a.M, out, a.n_cu, a.stream);
+    FQ_KRON_TRIO_LIST(X)
+#undef X
+    return FQ_LAUNCH_NO_KERNEL;
 }

@@ -20,7 +20,7 @@
 //     up with NT*16 consecutive n' of an output row = NT*8 contiguous bytes -> 16-byte stores.
 // LDS reads per 64x128 token: 16 (A) + 32 (R) + 8 (L) ds_read_b128 against 96 MFMAs.
 // bf16 activations (round 3, second session): the kernel is a template on the element type like the other path-A kernels (bf16 MFMA,
-// U / the optional Y rounding / the norm / the scale in bf16); fq_launch_kron_wave_bf16 serves the packed-only bf16 launches
+// U / the optional Y rounding / the norm / the scale in bf16); fq_launch_kron_wave (T = bf16) serves the packed-only bf16 launches
 // that used to run the workgroup-per-token kernel (64 x 128: 117 us against 77).
 #include "fq_common.hpp"
 #include "fq_dma.hpp"
@@ -450,11 +450,9 @@ template <int MT, int NT, int KS1, int W, bool RMS = false, typename T = f16, in
 int launch_wave(const T* x, const uint4* ws, int64_t rows, int M, const FqQuantOut& out, int n_cu, hipStream_t stream) {
     typedef WaveGeom<MT, NT, KS1, W> G;
     static_assert(G::LDS <= 160 * 1024, "LDS budget");
-    int64_t blocks = (rows + W - 1) / W;
-    if (blocks > n_cu) blocks = n_cu;  // one persistent workgroup per CU
-    if (blocks < 1) blocks = 1;
-    const int64_t tpb = (rows + blocks - 1) / blocks;
-    hipLaunchKernelGGL((fq_kron_wave_kernel<MT, NT, KS1, W, RMS, T, OS>), dim3((unsigned)blocks), dim3(W * 64), 0, stream, x, ws, rows,
+    int64_t tpb;
+    const unsigned blocks = fq_persistent_grid(rows, W, n_cu, &tpb);
+    hipLaunchKernelGGL((fq_kron_wave_kernel<MT, NT, KS1, W, RMS, T, OS>), dim3(blocks), dim3(W * 64), 0, stream, x, ws, rows,
                        tpb, M, out);
     return (int)hipGetLastError();
 }
@@ -472,53 +470,26 @@ int launch_wave(const T* x, const uint4* ws, int64_t rows, int M, const FqQuantO
 
 }  // namespace
 
-// Returns FQ_LAUNCH_NO_KERNEL when the shape / output set is not one this kernel covers (the caller falls back to the generic one).
 // ws: fragment workspace already filled by fq_kron_prepare_kernel (rfrag [NT][KS1][64], lfrag [2MT][MT][64]).
-template <typename T>
-static int launch_kron_wave_t(int flags, const T* x, const void* ws, const void* diag, int64_t rows, int M, int N,
-                              const FqQuantOut& out, int n_cu, hipStream_t stream) {
-    const bool rms = (flags & FQ_IN_RMSNORM) != 0;
-    const int ct = flags & FQ_CT_MASK & ~FQ_IN_RMSNORM;
-#ifndef WAVE_OS_MAXKS
-#define WAVE_OS_MAXKS 5   // 16-bit outputs on this kernel up to N = 16 x this = 80 (measured, profiles/r04_wave_fakequant.txt: the wider pairs — 128 elements per lane, two waves per SIMD — are faster on the workgroup-per-token kernel: 64 x 128 fake-quant 145 vs 121 us)
-#endif
-    const bool os_ok = N / 16 <= WAVE_OS_MAXKS;
-    const bool fq_only = os_ok && ct == FQ_OUT_FAKEQUANT && !rms && !(out.rt_flags & FQ_GROUP128);      // (round 4) 16-bit outputs, fp32 quantiser
-    const bool y_only = os_ok && (ct == FQ_OUT_TRANSFORM || ct == (FQ_OUT_TRANSFORM | FQ_QUANT_F16)) && !rms && !(out.rt_flags & FQ_GROUP128) && out.n_clips == 0;
-    if ((ct != FQ_OUT_PACKED && !fq_only && !y_only) || diag != nullptr) return FQ_LAUNCH_NO_KERNEL;
-    if ((fq_only && !out.fq[0]) || (y_only && !out.y)) return FQ_LAUNCH_NO_KERNEL;
-    if (M < 1 || M > 64 || (N & 15) || ((M * (N / 8)) & 63)) return FQ_LAUNCH_NO_KERNEL;
-    if ((out.rt_flags & FQ_GROUP128) && (N != 64 || (M & 1))) return FQ_LAUNCH_NO_KERNEL;  // groups = pairs of 64-element rows
-    const int MT = (M + 31) / 32, KS1 = N / 16;
-    const uint4* w = reinterpret_cast<const uint4*>(ws);
-    if (rms && !FqVec<T>::is_f16) return FQ_LAUNCH_NO_KERNEL;   // (deploy.nn.RMSNorm is an fp16 module: no bf16 instantiation with the norm)
-#define FQ_W(MT_, NT_, KS1_, W_)                                                                          \
-    if (MT == MT_ && KS1 == KS1_) {                                                                      \
-        if constexpr (FqVec<T>::is_f16) {                                                                \
-            if (rms) return launch_wave<MT_, NT_, KS1_, W_, true, T>(x, w, rows, M, out, n_cu, stream);  \
-        }                                                                                                \
-        if (fq_only) return launch_wave<MT_, NT_, KS1_, W_, false, T, FQ_OUT_FAKEQUANT>(x, w, rows, M, out, n_cu, stream); \
-        if (y_only) return launch_wave<MT_, NT_, KS1_, W_, false, T, FQ_OUT_TRANSFORM>(x, w, rows, M, out, n_cu, stream);   \
-        return launch_wave<MT_, NT_, KS1_, W_, false, T>(x, w, rows, M, out, n_cu, stream);              \
+template <int MT, int NT, int KS1, int W, typename T>
+static int launch_wave_os(const FqKronRoute& r, const FqKronArgs& a, const FqQuantOut& out) {
+    const T* x = (const T*)a.x;
+    const uint4* w = reinterpret_cast<const uint4*>(a.ws);
+    if constexpr (FqVec<T>::is_f16) {
+        if (r.t[4]) return launch_wave<MT, NT, KS1, W, true, T>(x, w, a.rows, a.M, out, a.n_cu, a.stream);
     }
-    FQ_W(2, 4, 8, 7)    // 64x128
-    FQ_W(2, 4, 7, 8)    // 64x112
-    FQ_W(2, 3, 5, 12)   // 64x80 (5120 = Qwen2.5-14B/32B hidden, in the reference's benchmark list: kernel_benchmark.py:234-246)
-    FQ_W(2, 2, 4, 16)   // 56x64, (64x64 stays with fq_kron64.hip)
-    FQ_W(1, 2, 4, 16)   // 32x64
-#undef FQ_W
+    if constexpr (KS1 <= WAVE_OS_MAXKS) {
+        if (r.t[6] == FQ_OUT_FAKEQUANT) return launch_wave<MT, NT, KS1, W, false, T, FQ_OUT_FAKEQUANT>(x, w, a.rows, a.M, out, a.n_cu, a.stream);
+        if (r.t[6] == FQ_OUT_TRANSFORM) return launch_wave<MT, NT, KS1, W, false, T, FQ_OUT_TRANSFORM>(x, w, a.rows, a.M, out, a.n_cu, a.stream);
+    }
+    return launch_wave<MT, NT, KS1, W, false, T>(x, w, a.rows, a.M, out, a.n_cu, a.stream);
+}
+
+int fq_launch_kron_wave(const FqKronRoute& r, const FqKronArgs& a, const FqQuantOut& out) {
+#define X(MT_, NT_, KS1_, W_)                                                                           \
+    if (r.t[0] == MT_ && r.t[2] == KS1_)                                                               \
+        return r.t[5] ? launch_wave_os<MT_, NT_, KS1_, W_, bf16>(r, a, out) : launch_wave_os<MT_, NT_, KS1_, W_, f16>(r, a, out);
+    FQ_KRON_WAVE_LIST(X)
+#undef X
     return FQ_LAUNCH_NO_KERNEL;
-}
-
-int fq_launch_kron_wave(int flags, const f16* x, const void* ws, const f16* diag, int64_t rows, int M, int N,
-                        const FqQuantOut& out, int n_cu, hipStream_t stream) {
-    return launch_kron_wave_t<f16>(flags, x, ws, diag, rows, M, N, out, n_cu, stream);
-}
-
-// the bf16 instantiations (called from fq_launch_kron_generic_bf16, fq_kron_generic2.hip; 64 x 64 stays with fq_kron64.hip)
-int fq_launch_kron_wave_bf16(int flags, const void* x, const void* ws, const void* diag, int64_t rows, int M, int N,
-                             const FqQuantOut& out, int n_cu, hipStream_t stream) {
-    if (M == 64 && N == 64) return FQ_LAUNCH_NO_KERNEL;
-    if (out.rt_flags & FQ_GROUP128) return FQ_LAUNCH_NO_KERNEL;   // (bf16 group-128 launches: the workgroup kernel's group epilogue)
-    return launch_kron_wave_t<bf16>(flags, (const bf16*)x, ws, diag, rows, M, N, out, n_cu, stream);
 }

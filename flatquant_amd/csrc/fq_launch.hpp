@@ -10,8 +10,12 @@ constexpr int FQ_LAUNCH_NO_KERNEL = -1000;   // no kernel is compiled for this f
 constexpr int FQ_LAUNCH_NEED_WS = -1001;     // the launch needs a (larger) workspace
 
 // ---- Kronecker transform + quantiser ----
-int fq_launch_kron64(int flags, const f16* x, const f16* left, const f16* right, const f16* diag,
-                     int64_t rows, const FqQuantOut& out, int n_cu, hipStream_t stream, const void* prep = nullptr);
+// WHICH kernel a launch runs is decided in one place, fq_kron_route (fq_kron_route.hpp, included here: the instantiation lists, the
+// order of preference, the shared preconditions). fq_launch_kron runs a route's kernel; the family launchers below it launch the
+// instantiation they are handed and return FQ_LAUNCH_NO_KERNEL only for one that is not in their list.
+#include "fq_kron_route.hpp"
+int fq_launch_kron64(int k64_flags, int bf16_dtype, const void* x, const void* left, const void* right, const void* diag, int64_t rows,
+                     const FqQuantOut& out, int n_cu, hipStream_t stream, const void* prep = nullptr);
 int fq_launch_kron64_prepare(const void* left, const void* right, void* image, hipStream_t stream);
 int fq_launch_kron64_linear(const f16* x, const void* prep, int64_t M, float rms_eps, bool rms, int rt_flags, int n, const void* const* wimg,
                             const f16* const* scol, const f16* const* bias, const float* sig_max, const float* sig_min, const int* N,
@@ -24,31 +28,31 @@ int fq_launch_kron64_trace(const f16* x, const f16* left, const f16* right, int6
 constexpr int64_t FQ_K64_IMAGE_BYTES = 16384, FQ_K64_WS_BYTES = 32768;
 int64_t fq_kron_generic_workspace_bytes(int M, int N);
 int fq_launch_kron_prepare(const f16* left, const f16* right, int M, int N, void* workspace, hipStream_t stream, int groups = 1);
+// fq_kron_route (without the 64 x 64 kernel), the fragment image unless FQ_WS_PREPARED, the launch. -> 0, a hipError_t, FQ_LAUNCH_NO_KERNEL / _NEED_WS.
 int fq_launch_kron_generic(int flags, const f16* x, const f16* left, const f16* right, const f16* diag,
                            int64_t rows, int M, int N, const FqQuantOut& out, void* workspace,
                            int64_t workspace_bytes, int n_cu, hipStream_t stream);
+int fq_launch_kron(const FqKronRoute& r, int flags, const f16* x, const f16* left, const f16* right, const f16* diag, int64_t rows, int M, int N,
+                   const FqQuantOut& out, void* workspace, int n_cu, hipStream_t stream);   // (the same after a route of the caller's)
 int fq_launch_kron_grouped_mats(int flags, const void* x, const void* left, const void* right, int64_t rows, int M, int N,
                                 const FqQuantOut& out, int n_groups, void* workspace, int64_t workspace_bytes, int n_cu,
                                 hipStream_t stream);
-// the kernel families fq_launch_kron_generic (fq_kron_generic.hip) and fq_launch_kron_generic_bf16 (fq_kron_generic2.hip) route to
-int fq_launch_kron_generic_bf16(int flags, const f16* x, const f16* left, const f16* right, const f16* diag, int64_t rows, int M, int N,
-                                const FqQuantOut& out, void* workspace, int64_t workspace_bytes, int n_cu, hipStream_t stream);
-int fq_launch_kron_g128_f16(int flags, const f16* x, const uint4* ws, const f16* diag, int64_t rows, int M, int N, const FqQuantOut& out,
-                            int n_cu, hipStream_t stream);
-int fq_launch_kron_general(int flags, const f16* x, const void* ws, const f16* diag, int64_t rows, int M, int N,
-                           const FqQuantOut& out, int n_cu, hipStream_t stream);
-int fq_launch_kron_wave(int flags, const f16* x, const void* ws, const f16* diag, int64_t rows, int M, int N,
-                        const FqQuantOut& out, int n_cu, hipStream_t stream);
-int fq_launch_kron_wave_bf16(int flags, const void* x, const void* ws, const void* diag, int64_t rows, int M, int N,
-                             const FqQuantOut& out, int n_cu, hipStream_t stream);
-int fq_launch_kron_trio(int flags, const f16* x, const void* ws, const f16* diag, int64_t rows, int M, int N,
-                        const FqQuantOut& out, int n_cu, hipStream_t stream);
-int fq_launch_kron_duo(int flags, const f16* x, const void* ws, const f16* diag, int64_t rows, int M, int N,
-                       const FqQuantOut& out, int n_cu, hipStream_t stream);
-int fq_launch_kron_tiles(int flags, const f16* x, const void* ws, const f16* diag, int64_t rows, int M, int N,
-                         const FqQuantOut& out, int n_cu, hipStream_t stream);
-int fq_launch_kron_tall(int flags, const f16* x, const void* ws, const f16* diag, int64_t rows, int M, int N,
-                        const FqQuantOut& out, int n_cu, hipStream_t stream);
+// the kernel families: r = the route (its family's); a.flags = the output set and run-time bits, x / diag = f16 or bf16 as r says, ws = the fragment image
+struct FqKronArgs {
+    int flags;
+    const void *x, *ws, *diag;
+    int64_t rows;
+    int M, N, n_cu;
+    hipStream_t stream;
+};
+int fq_launch_kron_wave(const FqKronRoute& r, const FqKronArgs& a, const FqQuantOut& out);
+int fq_launch_kron_tiles(const FqKronRoute& r, const FqKronArgs& a, const FqQuantOut& out);
+int fq_launch_kron_trio(const FqKronRoute& r, const FqKronArgs& a, const FqQuantOut& out);
+int fq_launch_kron_duo(const FqKronRoute& r, const FqKronArgs& a, const FqQuantOut& out);
+int fq_launch_kron_tall(const FqKronRoute& r, const FqKronArgs& a, const FqQuantOut& out);
+int fq_launch_kron_fast(const FqKronRoute& r, const FqKronArgs& a, const FqQuantOut& out);    // (f16: fq_kron_generic.hip)
+int fq_launch_kron_fast2(const FqKronRoute& r, const FqKronArgs& a, const FqQuantOut& out);   // (bf16, group-128: fq_kron_generic2.hip)
+int fq_launch_kron_general(const FqKronRoute& r, const FqKronArgs& a, const FqQuantOut& out);
 
 // ---- block-diagonal transform, Hadamard, row quantisers, elementwise ----
 int fq_launch_block(int flags, const f16* x, const f16* P, int64_t rows, int R, int C, int transpose_out,

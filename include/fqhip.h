@@ -828,6 +828,14 @@ int fq_sym_quant_f16(const void* x, const void* scale, int64_t rows, int cols, v
 int fq_sym_dequant_i32_f16(const void* q, const void* scale_row, const void* scale_col,
                            int64_t rows, int cols, void* x, void* stream);
 
+/* For tests and tools: WHICH kernel a Kronecker launch runs, as text in `buf` — the kernel's name with its template arguments,
+ * "fq_kron_tiles_kernel<3,4,128,3,6,0,f16,0>" (preparation kernels are not named), or the launcher's code ("-1000": no kernel for the
+ * shape / flags, "-1001": a (larger) workspace is needed). The launch's descriptors as plain arguments: form = 0 fq_kron_quant_*,
+ * 1 fq_rmsnorm_kron_quant[_ws]_f16, 2 fq_silu_mul_kron_quant_f16, 3 fq_kron_quant_ex_f16 (has_in2: `up` given), 4 fq_kron_quant_grouped_*;
+ * workspace_bytes = 0 without a workspace. Pure host arithmetic: no HIP call, no GPU needed. Returns strlen, or -1 if buf is too small. */
+int fq_debug_kron_route(int bf16_dtype, int form, int flags, int64_t rows, int M, int N, int n_clips, int has_diag, int has_in2,
+                        float post_scale, int64_t workspace_bytes, char* buf, int buf_bytes);
+
 const char* fq_last_error(void);
 int fq_version(void);
 

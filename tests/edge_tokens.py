@@ -19,17 +19,26 @@ SIGS = [(1.0, 1.0), (0.9820137619972229, 0.9820137619972229), (0.9, 0.33), (0.5,
         (3e-6, 1.0), (0.33, 0.9)]
 # what each entry is in the list for: the routes (see routes()) at least one row of the batch must take under it
 SIG_ROUTES = [{"plain"}, {"plain"}, {"plain", "clamp"}, {"clamp"}, {"plain"}, {"plain"}, {"div"}, {"plain", "clamp", "div"}, {"clamp"}]
-# the factor pairs, by the kernel fq_launch_kron_generic / kron_dispatch routes their packed-only launch to
+# the factor pairs, by the kernel family their packed-only fp16 launch runs (packed_family() below; the GPU tests hold the labels to it)
 PAIRS = {
-    "kron64": [(64, 64)],
+    "k64": [(64, 64)],
     "wave": [(32, 64), (56, 64), (64, 112), (64, 128)],
     "trio": [(112, 128), (128, 128)],
     "duo": [(112, 224), (128, 224)],
-    "tiles": [(80, 112), (86, 128), (128, 144), (128, 148), (144, 192)],
-    "tall": [(80, 64), (140, 64), (172, 64)],
+    # (N = 64, 64 < M <= 192 — the pairs fq_kron_tall.hip was written for — run the tiles kernel's N = 64 instantiations since round 5)
+    "tiles": [(80, 112), (86, 128), (128, 144), (128, 148), (144, 192), (80, 64), (140, 64), (172, 64)],
     "general": [(2, 2), (3, 6), (60, 62), (130, 16), (40, 100), (129, 254)],
 }
 ALL_PAIRS = [mn for fam in PAIRS.values() for mn in fam]
+FAMILY = {mn: fam for fam, pairs in PAIRS.items() for mn in pairs}
+
+
+def packed_family(M, N):
+    """the label a pair is filed under here and in tests/test_gpu_bounds.py, from the kernel fq_debug_kron_route names for its packed-only
+    fp16 launch (a host call: no GPU work)"""
+    from flatquant_amd import _lib
+    kernel = _lib.kron_route(M, N, 0x01).split("<")[0]
+    return {"fq_kron64_kernel": "k64", "fq_kron_fast_kernel": "table"}.get(kernel, kernel[len("fq_kron_"):-len("_kernel")])
 N_EDGE, N_BATCH = 12, 25
 NONFINITE_ROWS = (1, 3, 9)       # rows of the BATCH (edge rows 0, 1 and 4) that nonfinite() replaces
 

@@ -43,6 +43,7 @@ import torch
 from oracle import fq_oracle as O
 from tests import guards
 from tests.conftest import hadk_matrix, same_bits
+from tests.edge_tokens import packed_family
 
 pytestmark = pytest.mark.gpu
 P, F, T, R16, NC0, Q16, ASYM = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x800
@@ -215,18 +216,24 @@ def test_the_guard_bites_on_the_device():
 
 OUTPUT_SETS = [P, F, T, P | F | T, P | R16, P | NC0, P | Q16 | R16, P | F | T | R16]
 FULL_CROSS_PAIRS = [(64, 64), (64, 128), (128, 128), (20, 12)]        # the 64 x 64 path, the wave kernel, the workgroup-per-token table, the general kernel
+# the factor pairs, by the kernel family their packed-only fp16 launch runs (tests.edge_tokens.packed_family: asked of the library below)
 PAIRS = {
     "k64": [(64, 64)],
-    "wave": [(64, 128), (64, 112), (64, 80), (56, 64), (32, 64), (37, 64)],
-    "trio": [(112, 128), (86, 128), (128, 128), (80, 128)],
+    "wave": [(64, 128), (64, 112), (64, 80), (56, 64), (32, 64)],
+    "trio": [(112, 128), (128, 128)],
     "duo": [(128, 224)],
-    # every launch_tiles row of fq_kron_tiles.hip: both L depths (ceil(M / 16)) of N = 112 / 144 / 148 / 176 / 128, and 144 x 192
-    "tiles": [(80, 112), (96, 112), (128, 144), (112, 144), (128, 148), (112, 148), (144, 192), (168, 176), (178, 176)],
-    # N = 64, 64 < M <= 192: every FQ_T64 row (MT, ceil(M / 16)) = (3,5) (3,6) (4,7) (4,8) (5,9) (5,10) (6,11) (6,12)
-    "tall": [(80, 64), (96, 64), (112, 64), (128, 64), (140, 64), (160, 64), (172, 64), (192, 64)],
-    "table": [(96, 128), (112, 256), (32, 48), (100, 144)],
+    # every row of the tiles kernel's lists (csrc/fq_kron_route.hpp): both L depths (ceil(M / 16)) of N = 112 / 144 / 148 / 176 / 128, and 144 x 192;
+    # N = 64, 64 < M <= 192 (the pairs of fq_kron_tall.hip, on this kernel since round 5): every row (MT, ceil(M / 16)) = (3,5) (3,6) (4,7) (4,8)
+    # (5,9) (5,10) (6,11) (6,12). fq_kron_tall_kernel itself runs where a case asks for the fp32 quantiser WITH the transform (ROW_SETS has none:
+    # tests/test_gpu_kron_tall.py) or the rotation alone at M > 160 ((3, T, 1, False) at 172 x 64 and 192 x 64).
+    "tiles": [(80, 112), (96, 112), (128, 144), (112, 144), (128, 148), (112, 148), (144, 192), (168, 176), (178, 176), (86, 128), (80, 128),
+              (96, 128), (100, 144), (80, 64), (96, 64), (112, 64), (128, 64), (140, 64), (160, 64), (172, 64), (192, 64)],
+    "table": [(112, 256), (32, 48), (37, 64)],
     "general": [(2, 2), (3, 6), (20, 12), (60, 62), (130, 16), (129, 254), (256, 128)],
 }
+FAMILY = {mn: fam for fam, pairs in PAIRS.items() for mn in pairs}
+# 37 x 64: 37 rows of eight 16-byte pieces are no whole number of waves' lanes — the wave kernel declines, the workgroup-per-token table takes it
+WAVE_TEST_PAIRS = PAIRS["wave"] + [(37, 64)]
 # (rows, flags, clip sets, diag): every output set at some row count, the multi-clip loops, the instantiations with a compile-time output set
 ROW_SETS = [(1, P | F | T | R16, 4, False), (3, T, 1, False), (65, P | R16, 4, False), (65, P | Q16 | R16, 1, False), (65, P | NC0, 1, True),
             (65, P | F | T | R16, 2, False), (BIG, P, 1, False), (BIG, P | F | T | R16, 1, False)]
@@ -260,12 +267,13 @@ def test_kron_every_output_set(ops, M, N, flags, n_clips, diag):
 @pytest.mark.parametrize("rows,flags,n_clips,diag", ROW_SETS)
 @pytest.mark.parametrize("M,N", [mn for fam in PAIRS.values() for mn in fam])
 def test_kron_every_family_at_the_rows_with_tails(ops, M, N, rows, flags, n_clips, diag):
+    assert packed_family(M, N) == FAMILY[(M, N)]                     # (the label in PAIRS is the family that runs the pair)
     if rows == BIG and flags & F and M * N > 16384:
         rows = 519                                                   # (footprint: the 16-bit outputs of tokens above 32 KB)
     kron_case(ops, M, N, rows, flags, n_clips, diag)
 
 
-@pytest.mark.parametrize("M,N", PAIRS["wave"])
+@pytest.mark.parametrize("M,N", WAVE_TEST_PAIRS)
 @pytest.mark.parametrize("flags,n_clips", [(P, 1), (P | NC0, 4), (F | R16, 1), (T, 1)])
 def test_kron_wave_kernels_beyond_one_token_per_wave(ops, M, N, flags, n_clips):
     """W waves x n_cu workgroups hold at most 16 x 256 tokens at a time: at 4099 rows every workgroup gets 17 tokens and its waves run the slot
@@ -287,7 +295,7 @@ def test_kron_table_low_precision_quantiser_with_diag(ops, M, N, rows):
     kron_case(ops, M, N, rows, P | Q16 | R16, 1, True)
 
 
-@pytest.mark.parametrize("M,N", PAIRS["wave"])
+@pytest.mark.parametrize("M,N", WAVE_TEST_PAIRS)
 @pytest.mark.parametrize("rows", [2, BIG])
 def test_kron_wave_fake_quant_only(ops, M, N, rows):
     kron_case(ops, M, N, rows, F | R16, 1, False)

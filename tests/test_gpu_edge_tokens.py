@@ -104,6 +104,7 @@ def big_rows(M, N, flags):
 
 @pytest.mark.parametrize("M,N,lowp", CASES)
 def test_exact_factors_every_output_set_against_the_oracle(ops, M, N, lowp):
+    assert E.packed_family(M, N) == E.FAMILY[(M, N)]           # (the label in E.PAIRS is the family that runs the pair)
     b, L, R, y = exact_case(M, N, lowp)
     x, Ld, Rd = dev(b, lowp), dev(L, lowp), dev(R, lowp)
     for flags, sigs in [(f, E.SIGS) for f in PACKED_ONLY] + [(f, E.SIGS[:3]) for f in OTHER_SETS]:

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Which product kernels a rocprofv3 --kernel-trace run launched, by name WITH template arguments: tools/trace_kernel_names.py <trace dir>
 -> launches per kernel instantiation, the __global__ kernels of flatquant_amd/csrc (outside probe/) that never ran, and the rows of the Kronecker
-dispatch tables (FQ_F / FQ_FS / launch_tiles / FQ_T64) and the decode kernel's (QG, APPEND) pairs that ran or were MISSED.
+instantiation lists (csrc/fq_kron_route.hpp: the workgroup-per-token and the tiles kernel's) and the decode kernel's (QG, APPEND) pairs that ran or were MISSED.
 
 rocprofv3 leaves most of these names mangled (its demangler does not know _Float16 / __bf16), so the Itanium names are decoded here as far as
 kernel template arguments need: <len><name>, I ... E with L<type><value>E literals (i / j / l / m: integers, n = minus; b: bool) and the types
@@ -65,17 +65,21 @@ def main(trace_dir):
     print("\n".join(tables(cnt)))
 
 
-# The dispatch tables of fq_kron_generic.hip (FQ_F, FQ_FS: rows (MT, NT, KS1) of launch_fast) and fq_kron_tiles.hip (launch_tiles rows
-# (MT, NT, N, LKS); FQ_T64 rows (MT, LKS) at N = 64), restated here so that a trace can be held against them.
-FQ_F = [(2, 4, 8), (4, 4, 8), (3, 4, 8), (4, 7, 14), (2, 4, 7), (4, 8, 16), (1, 2, 4), (2, 2, 4), (2, 3, 5), (4, 5, 9), (3, 4, 7), (1, 2, 3), (5, 6, 12), (6, 6, 11)]
-FQ_FS = [(4, 4, 8), (3, 4, 8), (4, 7, 14), (4, 8, 16)]
-TILES = [(3, 4, 112, 5), (3, 4, 112, 6), (4, 5, 144, 7), (4, 5, 144, 8), (5, 6, 192, 9), (4, 5, 148, 7), (4, 5, 148, 8), (6, 6, 176, 11), (6, 6, 176, 12),
-         (3, 4, 128, 5), (3, 4, 128, 6), (4, 4, 128, 7), (4, 4, 128, 8)]
-T64 = [(3, 5), (3, 6), (4, 7), (4, 8), (5, 9), (5, 10), (6, 11), (6, 12)]
+def route_lists():
+    """the instantiation lists of csrc/fq_kron_route.hpp (the source the launch switches are generated from): list name -> rows of ints,
+    measurement knobs at their defaults"""
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "flatquant_amd", "csrc", "fq_kron_route.hpp")).read()
+    knobs = {"true": 1, "false": 0}
+    knobs.update({k: int(v) if v.isdigit() else knobs[v] for k, v in re.findall(r"^#define (\w+) (\d+|true|false)\b", src, re.M)})
+    lists = {}
+    for name, body in re.findall(r"^#define (FQ_KRON_\w+_LIST)\(X\)((?:.*\\\n)*.*)", src, re.M):
+        body = re.sub(r"/\*.*?\*/", "", body)
+        lists[name] = [tuple(int(t) if t.strip().isdigit() else knobs[t.strip()] for t in row.split(",")) for row in re.findall(r"X\(([^)]*)\)", body)]
+    return lists
 
 
 def tables(cnt):
-    """-> lines: every row of the tables above with the instantiations of it that ran (or MISSED), and the decode kernel's (QG, APPEND) pairs"""
+    """-> lines: every row of the route header's lists with the instantiations of it that ran (or MISSED), and the decode kernel's (QG, APPEND) pairs"""
     args = lambda n: [a.strip() for a in n[n.index("<") + 1:n.rindex(">")].split(",")]
     fast, tiles, dec = collections.defaultdict(set), collections.defaultdict(set), collections.Counter()
     for n in cnt:
@@ -88,19 +92,21 @@ def tables(cnt):
         if n.startswith("fq_kv_decode_kernel<"):
             a = args(n)     # HD, NW, UNI, F16, SPLIT, QG, APPEND
             dec[(int(a[5]), a[6] == "true")] += 1
-    out = ["# FQ_F rows (MT, NT, KS1) of launch_fast: CT = -1 every output set, 1 packed only, 33 packed with the fp16 quantiser (MT >= 3 only)"]
+    L = route_lists()
+    FQ_F, FQ_FS = [r[:3] for r in L["FQ_KRON_FAST_LIST"]], [r[:3] for r in L["FQ_KRON_FAST_SILU_LIST"]]
+    out = ["# FQ_KRON_FAST_LIST rows (MT, NT, KS1): CT = -1 every output set, 1 packed only, 33 packed with the fp16 quantiser (MT >= 3 only)"]
     for r in FQ_F:
         out.append(f"   {r}: " + (", ".join(sorted(fast[r + (False,)])) or "MISSED"))
-    out.append("# FQ_FS rows (SiLU.mul input)")
+    out.append("# FQ_KRON_FAST_SILU_LIST rows (SiLU.mul input)")
     for r in FQ_FS:
         out.append(f"   {r}: " + (", ".join(sorted(fast[r + (True,)])) or "MISSED"))
     other = sorted(k for k in fast if k[:3] not in FQ_F)
-    out.append("# launch_fast outside both tables (128 x 148 packed only = (4, 5, 10)): " + (", ".join(f"{k}: {sorted(fast[k])}" for k in other) or "none ran"))
-    out.append("# launch_tiles rows (MT, NT, N, LKS)")
-    for r in TILES:
-        out.append(f"   {r}: " + (", ".join(sorted(tiles[r])) or "MISSED"))
-    out.append("# FQ_T64 rows (MT, LKS) at N = 64")
-    for mt, lks in T64:
+    out.append("# fq_kron_fast_kernel outside both lists: " + (", ".join(f"{k}: {sorted(fast[k])}" for k in other) or "none ran"))
+    out.append("# FQ_KRON_TILES_LIST rows (MT, NT, N, LKS)")
+    for r in L["FQ_KRON_TILES_LIST"]:
+        out.append(f"   {(r[0], r[1], r[2], r[4])}: " + (", ".join(sorted(tiles[(r[0], r[1], r[2], r[4])])) or "MISSED"))
+    out.append("# FQ_KRON_TILES64_LIST rows (MT, LKS) at N = 64")
+    for mt, lks, _ in L["FQ_KRON_TILES64_LIST"]:
         out.append(f"   ({mt}, {lks}): " + (", ".join(sorted(tiles[(mt, 2, 64, lks)])) or "MISSED"))
     out.append("# fq_kv_decode_kernel (QG, APPEND) -> instantiations that ran: " + ", ".join(f"{k}: {v}" for k, v in sorted(dec.items())))
     return out
