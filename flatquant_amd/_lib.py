@@ -123,6 +123,8 @@ SYMBOLS = {
     "fq_block_quant_f16": (_i, [_vp, _vp, _i64, _i, _i, _i, _fp, _fp, _i, _i, _vpp, _vpp, _vpp, _vp, _vp]),
     "fq_int4_gemm_i32": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp]),
     "fq_int4_linear_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),
+    "fq_int4_gemm_grouped_i32": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i, _vp, _vp]),
+    "fq_int4_linear_grouped_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _i, _vp, _vp]),
     "fq_hadamard_f16": (_i, [_vp, _vp, _i64, _i, _i, _vp, _f, _vp]),
     "fq_fwht_f32_f16": (_i, [_vp, _vp, _i64, _i, _f, _vp]),
     "fq_plan_kron": (_vp, [_i, _vp, _vp, _i64, _i, _i, _f, _f, _i, _vp, _i64]),

@@ -150,7 +150,7 @@ static int kron_dispatch(const char* what, const FqQuantOut& o, int flags, const
 extern "C" {
 
 const char* fq_last_error(void) { return g_err; }
-int fq_version(void) { return 120; }
+int fq_version(void) { return 121; }
 
 static int kron_quant_impl(const char* what, int dt, const void* x, const void* left, const void* right, const void* diag, int64_t rows,
                            int M, int N, const float* sig_max, const float* sig_min, int n_clips, int flags,
@@ -664,6 +664,42 @@ int fq_int4_linear_f16(const void* x, const void* x_scale, const void* w, const 
                                      (const f16*)w_scale, (const f16*)bias, (hipStream_t)stream);
     if (rc == FQ_LAUNCH_NO_KERNEL) return fail(FQ_EUNSUPPORTED, "fq_int4_linear_f16: shape M=%lld N=%d K=%d not supported (K < 2^25)", (long long)M, N, K);
     return check_launch(rc, "fq_int4_linear_f16");
+}
+
+// The sizes of the grouped GEMM entry points (everything below returns before any HIP call). K: the dense entry points' rules.
+static int gemm_grouped_sizes(const char* what, const int64_t* group_offsets, int64_t rows, int N, int K, int n_groups) {
+    if (reinterpret_cast<uintptr_t>(group_offsets) & 7u) return fail(FQ_EINVAL, "%s: group_offsets is not 8-byte aligned", what);
+    if (rows < 0 || N < 1 || K < 1 || n_groups < 1)
+        return fail(FQ_EINVAL, "%s: bad sizes rows=%lld N=%d K=%d n_groups=%d", what, (long long)rows, N, K, n_groups);
+    if (n_groups > 1024) return fail(FQ_EUNSUPPORTED, "%s: n_groups=%d (at most 1024)", what, n_groups);
+    if (K % 32) return fail(FQ_EUNSUPPORTED, "%s: K=%d must be a multiple of 32", what, K);
+    if (K >= (1 << 25) || rows > (1 << 30))
+        return fail(FQ_EUNSUPPORTED, "%s: shape rows=%lld N=%d K=%d not supported (K < 2^25, rows <= 2^30)", what, (long long)rows, N, K);
+    return FQ_OK;
+}
+
+int fq_int4_gemm_grouped_i32(const void* x, const void* w_g, int64_t rows, int N, int K, const int64_t* group_offsets, int n_groups,
+                             void* c, void* stream) {
+    const char* what = "fq_int4_gemm_grouped_i32";
+    if (!x || !w_g || !c || !group_offsets) return fail(FQ_EINVAL, "%s: NULL pointer", what);
+    FQ_NEED_ALIGN16(what, x, w_g, c);
+    const int bad = gemm_grouped_sizes(what, group_offsets, rows, N, K, n_groups);
+    if (bad != FQ_OK) return bad;
+    if (rows == 0) return FQ_OK;
+    return check_launch(fq_launch_gemm_i4_grouped((const uint8_t*)x, (const uint8_t*)w_g, rows, N, K, group_offsets, n_groups, (int32_t*)c,
+                                                  nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream), what);
+}
+
+int fq_int4_linear_grouped_f16(const void* x, const void* x_scale, const void* w_g, const void* w_scale_g, const void* bias_g, int64_t rows,
+                               int N, int K, const int64_t* group_offsets, int n_groups, void* y, void* stream) {
+    const char* what = "fq_int4_linear_grouped_f16";
+    if (!x || !x_scale || !w_g || !w_scale_g || !y || !group_offsets) return fail(FQ_EINVAL, "%s: NULL pointer", what);
+    FQ_NEED_ALIGN16(what, x, w_g, y, w_scale_g, bias_g);   // (the epilogue reads w_scale_g / bias_g with 16-byte loads)
+    const int bad = gemm_grouped_sizes(what, group_offsets, rows, N, K, n_groups);
+    if (bad != FQ_OK) return bad;
+    if (rows == 0) return FQ_OK;
+    return check_launch(fq_launch_gemm_i4_grouped((const uint8_t*)x, (const uint8_t*)w_g, rows, N, K, group_offsets, n_groups, nullptr, (f16*)y,
+                                                  (const f16*)x_scale, (const f16*)w_scale_g, (const f16*)bias_g, (hipStream_t)stream), what);
 }
 
 int64_t fq_int4_frag_bytes(int N, int K) { return fq_i4_frag_bytes(N, K); }

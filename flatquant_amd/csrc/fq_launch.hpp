@@ -88,6 +88,9 @@ int fq_launch_rope(f16* q_out, f16* k_out, const f16* q, const f16* k, const f16
 // ---- GEMMs ----
 int fq_launch_gemm_i4(const uint8_t* X, const uint8_t* W, int64_t M, int N, int K, int32_t* c, f16* y, const f16* srow,
                       const f16* scol, const f16* bias, hipStream_t stream);
+// every expert's GEMM as one launch (fq_gemm_i4_grouped.hip): rows sorted by group, w / scol / bias stacked per group, offsets on the device
+int fq_launch_gemm_i4_grouped(const uint8_t* X, const uint8_t* Wg, int64_t rows, int N, int K, const int64_t* group_offsets, int n_groups,
+                              int32_t* c, f16* y, const f16* srow, const f16* scol_g, const f16* bias_g, hipStream_t stream);
 int64_t fq_i4_frag_bytes(int N, int K);
 int fq_launch_i4_to_frag(const uint8_t* W, int N, int K, void* img, int n_cu, hipStream_t stream);
 int fq_launch_gemm_i4_skinny(const uint8_t* X, const void* wimg, int64_t M, int N, int K, int32_t* c, f16* y, const f16* srow,

@@ -218,7 +218,70 @@ class Linear4bit(torch.nn.Module):
         return int_module
 
 
-WIDE_DECODE_ROWS = 33          # linear4bit_multi: from this many rows a group of >= WIDE_DECODE_FEATURES output features takes the FP6 tile kernel
+class Linear4bitGrouped(torch.nn.Module):
+    """The ``Linear4bit`` layers of the experts of one mixture-of-experts projection (all w1, all w3 or all w2) as ONE module and one
+    launch.  AN EXTENSION: the reference has no counterpart (its DeepSeek-V3 path, flatquant/model_tools/deepseekv3_utils.py, is
+    fake-quant only and loops over the experts on the host); documented as such, like ``share_kv_heads`` of the paged cache.
+    Buffers are ``Linear4bit``'s, stacked over the experts: ``weight`` uint8 [E, out, in/2], ``weight_scales`` [E, out, 1], optional
+    ``bias`` [E, out].  ``forward(packed, group_offsets)`` takes the PackedQuantizedTensor of ``ops.kron_quant_grouped(FQ_OUT_PACKED)``
+    — rows sorted by expert, per-token scales — and the int64 DEVICE offsets [E + 1] of ``ops.moe_group_rows``, and returns fp16
+    [rows, out], bit-identical to ``Linear4bit`` number e applied to the rows [group_offsets[e], group_offsets[e+1]) for every e
+    (fq_int4_linear_grouped_f16). Nothing is read back to the host, so a step that contains it can be captured in a graph.
+    The int8 matrix path only: no FP6 image, no decode image (candidates for later work: DESIGN.md)."""
+
+    def __init__(self, n_experts, in_features, out_features, bias=False, dtype=torch.float16):
+        super().__init__()
+        self.n_experts = n_experts
+        self.in_features = in_features
+        self.out_features = out_features
+        self.register_buffer("weight_scales", torch.zeros((n_experts, out_features, 1), requires_grad=False))
+        self.register_buffer("weight", torch.randint(1, 7, (n_experts, out_features, in_features // 2), dtype=torch.uint8, requires_grad=False))
+        if bias:
+            self.register_buffer("bias", torch.zeros((n_experts, out_features), dtype=dtype))
+        else:
+            self.bias = None
+        ops.invalidate_on_load(self)
+
+    def _scales16(self):
+        """(weight_scales [E, out] and bias as contiguous fp16, or None), converted once per buffer version, as Linear4bit._scales16"""
+        b = self.bias
+        key = (self.weight_scales.data_ptr(), ops.ver(self.weight_scales), None if b is None else (b.data_ptr(), ops.ver(b)), ops.cache_epoch())
+        if getattr(self, "_s16_key", None) != key:
+            self._s16 = (self.weight_scales.reshape(self.n_experts, self.out_features).to(torch.float16).contiguous(),
+                         None if b is None else b.to(torch.float16).contiguous())
+            self._s16_key = key
+        return self._s16
+
+    def forward(self, x, group_offsets):
+        assert isinstance(x, PackedQuantizedTensor)
+        q = x.quantized_x
+        ws16, b16 = self._scales16()
+        y = ops.int4_linear_grouped(q.reshape(-1, q.shape[-1]).contiguous(), x.scales_x.reshape(-1).contiguous(), self.weight, ws16,
+                                    group_offsets, b16)
+        return y.view(*q.shape[:-1], self.out_features)
+
+    @staticmethod
+    def from_float(linears, weight_scales=None):
+        """From the experts' ``torch.nn.Linear`` (one shape, all with or all without bias) and their weight scales (a sequence of
+        [out, 1] tensors or one [E, out, 1] tensor): each expert packed exactly as ``Linear4bit.from_float`` packs it."""
+        linears = list(linears)
+        first = linears[0]
+        assert all(m.in_features == first.in_features and m.out_features == first.out_features and (m.bias is None) == (first.bias is None)
+                   for m in linears), "the experts must share one shape and either all or none carry a bias"
+        int_module = Linear4bitGrouped(len(linears), first.in_features, first.out_features, bias=first.bias is not None,
+                                       dtype=first.weight.dtype).to(first.weight.dtype)
+        if weight_scales is not None:
+            assert len(weight_scales) == len(linears)
+            for e, (m, s) in enumerate(zip(linears, weight_scales)):
+                one = Linear4bit.from_float(m, s)
+                int_module.weight_scales[e].copy_(one.weight_scales)
+                int_module.weight[e].copy_(one.weight)
+                if m.bias is not None:
+                    int_module.bias[e].copy_(one.bias)
+        return int_module
+
+
+WIDE_DECODE_ROWS = 33         # linear4bit_multi: from this many rows a group of >= WIDE_DECODE_FEATURES output features takes the FP6 tile kernel
 WIDE_DECODE_FEATURES = 16384
 
 

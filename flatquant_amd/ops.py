@@ -2167,6 +2167,53 @@ def int4_linear(x: torch.Tensor, x_scale: torch.Tensor, w: torch.Tensor, w_scale
     return y
 
 
+def _chk_grouped_gemm(what: str, x: torch.Tensor, w_g: torch.Tensor, group_offsets: torch.Tensor):
+    """The operands every grouped GEMM shares -> (rows, n_groups, N, K). Nothing here reads a tensor's contents."""
+    _chk(x, "x", torch.uint8), _chk(w_g, "w_g", torch.uint8), _chk(group_offsets, "group_offsets", torch.int64)
+    if x.dim() != 2 or w_g.dim() != 3 or x.shape[1] != w_g.shape[2]:
+        raise RuntimeError(f"{what}: expected x [rows, K/2] and w_g [n_groups, N, K/2], got {tuple(x.shape)} and {tuple(w_g.shape)}")
+    G = w_g.shape[0]
+    if group_offsets.dim() != 1 or group_offsets.numel() != G + 1:
+        raise RuntimeError(f"{what}: group_offsets must have n_groups + 1 = {G + 1} entries, got {tuple(group_offsets.shape)}")
+    if group_offsets.device != x.device or w_g.device != x.device:
+        raise RuntimeError(f"{what}: x, w_g and group_offsets must be on one device")
+    return x.shape[0], G, w_g.shape[1], x.shape[1] * 2
+
+
+def int4_matmul_grouped(x: torch.Tensor, w_g: torch.Tensor, group_offsets: torch.Tensor) -> torch.Tensor:
+    """int4_matmul of every group (expert) in one launch (fq_int4_gemm_grouped_i32): x uint8 [rows, K/2] sorted by group, group g owns rows
+    [group_offsets[g], group_offsets[g+1]) and multiplies with w_g[g] (uint8 [n_groups, N, K/2]) -> int32 [rows, N]. group_offsets is the int64
+    device tensor of moe_group_rows / kron_quant_grouped; nothing is read back (capturable). Bit-identical to int4_matmul per row slice."""
+    rows, G, N, K = _chk_grouped_gemm("int4_matmul_grouped", x, w_g, group_offsets)
+    c = torch.empty((rows, N), dtype=torch.int32, device=x.device)
+    if rows == 0:
+        return c
+    with _on(x.device):
+        check(lib.fq_int4_gemm_grouped_i32(_ptr(x), _ptr(w_g), rows, N, K, _ptr(group_offsets), G, _ptr(c), _stream(x)))
+    return c
+
+
+def int4_linear_grouped(x: torch.Tensor, x_scale: torch.Tensor, w_g: torch.Tensor, w_scale_g: torch.Tensor, group_offsets: torch.Tensor,
+                        bias_g: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Linear4bit.forward of every group (expert) in one launch (fq_int4_linear_grouped_f16): the packed rows and per-token fp16 scales
+    [rows] of kron_quant_grouped(FQ_OUT_PACKED), w_g uint8 [n_groups, N, K/2], w_scale_g fp16 [n_groups, N], optional bias_g fp16
+    [n_groups, N] -> fp16 [rows, N]. An extension (the reference's MoE path is fake-quant only); bit-identical to int4_linear on each
+    group's row slice, without the host loop and the ``offsets.tolist()`` it needs."""
+    rows, G, N, K = _chk_grouped_gemm("int4_linear_grouped", x, w_g, group_offsets)
+    _chk(x_scale, "x_scale"), _chk(w_scale_g, "w_scale_g")
+    if bias_g is not None:
+        _chk(bias_g, "bias_g")
+    if x_scale.numel() != rows or w_scale_g.numel() != G * N or (bias_g is not None and bias_g.numel() != G * N):
+        raise RuntimeError("int4_linear_grouped: scale / bias sizes do not match rows / n_groups x N")
+    y = torch.empty((rows, N), dtype=torch.float16, device=x.device)
+    if rows == 0:
+        return y
+    with _on(x.device):
+        check(lib.fq_int4_linear_grouped_f16(_ptr(x), _ptr(x_scale), _ptr(w_g), _ptr(w_scale_g), _ptr(bias_g), rows, N, K,
+                                             _ptr(group_offsets), G, _ptr(y), _stream(x)))
+    return y
+
+
 def sym_quant(x: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     """_CUDA.sym_quant (bindings.cpp:27-44): x fp16 [rows, cols], scale fp16 [rows] -> uint8 [rows, ceil(cols/2)]."""
     _chk(x, "x"), _chk(scale, "scale")

@@ -836,6 +836,25 @@ int fq_sym_dequant_i32_f16(const void* q, const void* scale_row, const void* sca
 int fq_debug_kron_route(int bf16_dtype, int form, int flags, int64_t rows, int M, int N, int n_clips, int has_diag, int has_in2,
                         float post_scale, int64_t workspace_bytes, char* buf, int buf_bytes);
 
+/*
+ * Grouped INT4 GEMM / Linear4bit (version 121): every expert's fq_int4_gemm_i32 / fq_int4_linear_f16 of a mixture-of-experts layer as ONE
+ * launch, the consumer of fq_kron_quant_grouped_*'s FQ_OUT_PACKED rows.  c[r][n] = sum_k x[r][k] * w_g[g(r)][n][k], g(r) the group with
+ * group_offsets[g] <= r < group_offsets[g+1].  An extension (the reference's MoE path is fake-quant only).
+ * Contract: bit-identical to fq_int4_linear_f16 / fq_int4_gemm_i32 called once per group on that group's row slice and weights.
+ *   x [rows, K/2] uint8, rows sorted by group (q_out of the grouped transform); x_scale [rows] fp16 (its per-token scale_out);
+ *   w_g [n_groups, N, K/2] uint8 contiguous; w_scale_g [n_groups, N] fp16; bias_g [n_groups, N] fp16 or NULL;
+ *   c [rows, N] int32; y [rows, N] fp16.
+ *   group_offsets: DEVICE int64 [n_groups + 1], non-decreasing, [0] = 0, [n_groups] = rows, empty groups allowed — the contract of
+ *   fq_kron_quant_grouped_f16. Trusted, never read on the host: nothing is read back, no synchronisation, capturable in a graph.
+ * rows == 0: FQ_OK without a launch. 1 <= n_groups <= 1024 (FQ_EUNSUPPORTED above). K % 32 == 0 and K < 2^25, as the dense entry
+ * points (FQ_EUNSUPPORTED otherwise); K % 128 == 0, N % 16 == 0, K < 2^17 run the int8 matrix path, every other shape a general kernel.
+ * Per-token activation scales and fp16 output only (no FQ_GROUP128 scales, no FP6 matrix path, no bf16).
+ */
+int fq_int4_gemm_grouped_i32(const void* x, const void* w_g, int64_t rows, int N, int K,
+                             const int64_t* group_offsets, int n_groups, void* c, void* stream);
+int fq_int4_linear_grouped_f16(const void* x, const void* x_scale, const void* w_g, const void* w_scale_g, const void* bias_g,
+                               int64_t rows, int N, int K, const int64_t* group_offsets, int n_groups, void* y, void* stream);
+
 const char* fq_last_error(void);
 int fq_version(void);
 
