@@ -268,12 +268,19 @@ __device__ __forceinline__ float fq_group4_reduce(float v, Op op) {
 //     y is at least 2^-24, and an fp32 y (no FQ_ROUND_Y_F16) is an fp32 sum of products of fp16 values, each a multiple of 2^-48, so it is
 //     0 or at least 2^-48 — times 2^100 beyond 8 either way. y / 2^-100 stays finite in fp32 (m < 7 x 2^-25), so no Inf x 0 arises in the
 //     reciprocal forms. The quantisers that divide in T by (T)scale == 0 (fq_quant1_h) make the NaN of 0 / 0 digit 0 themselves.
-//   T = bf16: NOT covered. A bf16 scale underflows only for m <= 3 x 2^-133 (bf16 has fp32's exponent range); no fp32 normal rounds to a
-//     bf16 zero, so such a token stores 2^-100 and gets all-zero digits where the reference saturates. No model activation comes near.
+//   T = bf16: NOT covered by the fused kernels. A bf16 scale underflows only for m <= 3 x 2^-133 (bf16 has fp32's exponent range); no fp32
+//     normal rounds to a bf16 zero, so such a token stores 2^-100 and gets all-zero digits where the reference saturates. No model
+//     activation comes near. The standalone row quantisers (fq_quant.hip, ROWQ) do cover it: every one of their bf16 quantisers divides
+//     in T by (T)scale, so they take FQ_SCALE_UNDERFLOW_BF16, an fp32 subnormal that is only ever converted to bf16 — to 0.
 constexpr float FQ_SCALE_UNDERFLOW = 0x1p-100f;
+constexpr float FQ_SCALE_UNDERFLOW_BF16 = 0x1p-140f;
+template <typename T, bool ROWQ>
+__device__ __forceinline__ float fq_scale_underflow() {
+    return (ROWQ && !FqVec<T>::is_f16) ? FQ_SCALE_UNDERFLOW_BF16 : FQ_SCALE_UNDERFLOW;
+}
 
 // scale from (xmax, xmin) of one token and one clip set; see header comment for the pinned arithmetic.
-template <int FLAGS, typename T = f16>
+template <int FLAGS, typename T = f16, bool ROWQ = false>
 __device__ __forceinline__ float fq_token_scale(float xmax, float xmin, float sig_max, float sig_min,
                                                 int rt_flags) {
     if (!(rt_flags & FQ_NO_CLAMP0)) {
@@ -284,7 +291,10 @@ __device__ __forceinline__ float fq_token_scale(float xmax, float xmin, float si
         // deploy Quantizer(input_clip_ratio) (deploy/nn/quantization.py:30): (max|x| / 7).to(fp16) * ratio, both steps in T
         const float m0 = fmaxf(fabsf(xmin), xmax);
         if (m0 == 0.0f) return 1.0f;   // (quantise with 1: every digit is 0; the caller stores the reference's scale, 0)
-        return (float)fq_mul_to<T>((float)(T)(m0 / 7.0f), sig_max);   // (can underflow to 0 as well: not handled, see FQ_SCALE_UNDERFLOW)
+        const float s = (float)fq_mul_to<T>((float)(T)(m0 / 7.0f), sig_max);
+        // (the quotient or the product can underflow to 0, and the reference divides by the 0 it stores: the standalone row quantisers
+        //  handle it like FQ_SCALE_UNDERFLOW below; the Kronecker launch that takes this flag does not)
+        return (ROWQ && s == 0.0f) ? fq_scale_underflow<T, ROWQ>() : s;
     }
     if ((FLAGS & FQ_QUANT_F16) && (rt_flags & FQ_SIG_F16)) {
         // deploy.nn.Quantizer(lac=True), deploy/nn/quantization.py:21-22: an fp16 [rows, 1] tensor times a 0-dim fp32
@@ -307,7 +317,7 @@ __device__ __forceinline__ float fq_token_scale(float xmax, float xmin, float si
         // (T = bf16: the fp32 quotient of two 8-bit significands rounded to bf16 is the correctly rounded bf16 quotient)
         scale = (float)(T)(m / 7.0f);
         if (m == 0.0f) scale = 1.0f;
-        else if (scale == 0.0f) scale = FQ_SCALE_UNDERFLOW;
+        else if (scale == 0.0f) scale = fq_scale_underflow<T, ROWQ>();
     } else {
         scale = m / 7.0f;
         if (m == 0.0f) scale = 1.0f;

@@ -51,7 +51,7 @@ __global__ __launch_bounds__(RQ_THREADS) void fq_rowquant_kernel(const T* __rest
         vmin = fminf(fminf(red[1][0], red[1][1]), fminf(red[1][2], red[1][3]));
 
         for (int ci = 0; ci < out.n_clips; ++ci) {
-            const float scale = fq_token_scale<FLAGS, T>(vmax, vmin, out.sig_max[ci], out.sig_min[ci], out.rt_flags);
+            const float scale = fq_token_scale<FLAGS, T, true>(vmax, vmin, out.sig_max[ci], out.sig_min[ci], out.rt_flags);
             const float h16_inv = fq_fast_inv(scale);
             const FqH16Recip h16rc = ((FLAGS & FQ_QUANT_F16) && IS16) ? fq_h16_recip(scale) : FqH16Recip{0.0f, 0.0f};
             const bool h16_clamp = fq_h16_needs_clamp(vmax, vmin, h16_inv);
@@ -67,6 +67,9 @@ __global__ __launch_bounds__(RQ_THREADS) void fq_rowquant_kernel(const T* __rest
                             const u32x4 xv = __builtin_bit_cast(u32x4, v[k]);
                             d = h16_clamp ? fq_quant8_h16<true>(xv[0], xv[1], xv[2], xv[3], h16rc)
                                           : fq_quant8_h16<false>(xv[0], xv[1], xv[2], xv[3], h16rc);
+                        } else if (FLAGS & FQ_QUANT_F16) {   // bf16 arithmetic: the quotient rounded to bf16, by the scale as stored
+#pragma unroll
+                            for (int e = 0; e < 8; ++e) d |= (uint32_t)(fq_quant1_h(v[k][e], (T)scale) & 15) << (4 * e);
                         } else {
 #pragma unroll
                             for (int e = 0; e < 8; ++e)
@@ -211,8 +214,11 @@ void fq_rowquant_wave_kernel(const T* __restrict__ x, int64_t rows, int cols,
             vmin = fq_wave_min(vmin);
         }
         for (int ci = 0; ci < out.n_clips; ++ci) {
-            const float scale = fq_token_scale<FLAGS, T>(vmax, vmin, out.sig_max[ci], out.sig_min[ci], out.rt_flags);
+            const float scale = fq_token_scale<FLAGS, T, true>(vmax, vmin, out.sig_max[ci], out.sig_min[ci], out.rt_flags);
             const float inv = fq_fast_inv(scale);
+            // an fp32 scale below the normal range (a bf16 row of values near 2^-120 under a small clip pair): v_rcp_f32 returns Inf for it,
+            // 0 x Inf is a NaN that neither dmax nor the clamp keeps — such a row asks for the division itself, like a near-tie does
+            const bool tiny = scale < 0x1p-126f;
             const FqH16Recip h16rc = ((FLAGS & FQ_QUANT_F16) && IS16) ? fq_h16_recip(scale) : FqH16Recip{0.0f, 0.0f};
             const bool h16_clamp = fq_h16_needs_clamp(vmax, vmin, inv);
             if (FLAGS & FQ_OUT_PACKED) {
@@ -238,7 +244,7 @@ void fq_rowquant_wave_kernel(const T* __restrict__ x, int64_t rows, int cols,
                         const f32x2 q45 = fq_qfast2(f32x2{(float)v[k][4], (float)v[k][5]}, inv2, dmax);
                         const f32x2 q67 = fq_qfast2(f32x2{(float)v[k][6], (float)v[k][7]}, inv2, dmax);
                         d = fq_pack8(q01.x, q01.y, q23.x, q23.y, q45.x, q45.y, q67.x, q67.y);
-                        if (fq_wave_needs_exact(dmax))
+                        if (fq_wave_needs_exact(tiny ? 1.0f : dmax))
                             d = fq_pack8(fq_qexact((float)v[k][0], scale), fq_qexact((float)v[k][1], scale),
                                          fq_qexact((float)v[k][2], scale), fq_qexact((float)v[k][3], scale),
                                          fq_qexact((float)v[k][4], scale), fq_qexact((float)v[k][5], scale),
@@ -262,7 +268,7 @@ void fq_rowquant_wave_kernel(const T* __restrict__ x, int64_t rows, int cols,
                         float r[8];
 #pragma unroll
                         for (int e = 0; e < 8; ++e) r[e] = fq_qfast((float)v[k][e], inv, dmax);
-                        if (fq_wave_needs_exact(dmax)) {
+                        if (fq_wave_needs_exact(tiny ? 1.0f : dmax)) {
 #pragma unroll
                             for (int e = 0; e < 8; ++e) r[e] = fq_qexact((float)v[k][e], scale);
                         }
@@ -349,7 +355,7 @@ int launch_rowquant(const T* x, int64_t rows, int cols, const FqQuantOut& out, i
         hipLaunchKernelGGL((fq_rowquant_kernel<FLAGS, (N), T>), g, b, 0, stream, x, rows, cols, out); \
         return (int)hipGetLastError();                                                           \
     }
-    FQ_RQ(2) FQ_RQ(4) FQ_RQ(8) FQ_RQ(RQ_MAXCH)
+    FQ_RQ(8) FQ_RQ(RQ_MAXCH)  // (a row that gets here has more than 1536 chunks: nch >= 7)
 #undef FQ_RQ
     return FQ_LAUNCH_NO_KERNEL;
 }
@@ -659,8 +665,11 @@ __global__ __launch_bounds__(256) void fq_fakequant_bits_kernel(const T* __restr
                     q = __builtin_amdgcn_fmed3f(rnd(q + zero), 0.0f, qmax);
                     o[e] = fq_mul_to<T>(scale, q - zero);
                 } else {
-                    q = __builtin_amdgcn_fmed3f(q, -qmax - 1.0f, qmax);
-                    o[e] = fq_fake<T>(scale, q);            // (+0.0 for a zero digit, like the 4-bit kernels)
+                    q = __builtin_amdgcn_fmed3f(q, -qmax - 1.0f, qmax) + 0.0f;   // (+0 for a zero digit: rint of a small negative quotient is -0)
+                    if (t != t) q = 0.0f;                                         // 0 / 0 under an underflowed scale: digit 0, as fq_quant1_h
+                    // like the 4-bit kernels' integer digit: +0.0 for a zero digit, and 0 x q = -0.0 for a negative digit under an
+                    // underflowed 16-bit scale (the plain product; fq_fake's p + 0 would make that +0.0)
+                    o[e] = fq_mul_to<T>(scale, q);
                 }
             }
             yp[i] = __builtin_bit_cast(uint4, o);
